@@ -1,12 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: volumes/sec of the CoMA-UNet training step at 128^3, batch 2 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One step = forward + GenerativeContrastiveLoss + backward + gradient all-reduce (N > 1) + fused
 AdamW on one batch of seeded synthetic volumes already resident in HBM.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` then also writes what the last
+timed step computed (see dump_outputs).  Everything below needs runs of its own and is measured only
+with `--full`:
  * `roofline`: the dominant KERNEL of the step by summed time (by name, as rocprofv3 prints it -- the library reports the
    variant each dispatch launched, coma_last_kernel; normalisation launches are bracketed too): achieved = summed
    algorithmic FLOPs (MFMA-bound) or bytes (HBM-bound) of its launches / summed launch durations, measured live with HIP
@@ -21,6 +26,7 @@ Rank 0 prints ONE JSON line.
  * `cpu_baseline`: the CPU oracle (this repo's restatement of the reference path -- the reference itself cannot be
    imported) timed on the host cores: 1 warm-up + median of 3 fwd+bwd steps, rank 0, N = 1 only.
  * `parity`: rel-L2 and voxel MAE of THIS run's model (same weights, same inputs) against that oracle's forward.
+ * `data_parallel` (N > 1): the exchange alone, the step without it, and the part of the exchange the step exposes.
 """
 import argparse
 import json
@@ -42,10 +48,15 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_BF16_PEAK_TFLOPS = 2500.0    # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_BF16_PEAK_TFLOPS = 2500.0    # dense bf16 MFMA peak of the MI355X
 FP32_VALU_PEAK_TFLOPS = 157.3     # = the fp32 MFMA peak (v_mfma_f32_32x32x2_f32 runs at the vector rate)
 HBM_PEAK_GBPS = 8000.0
 UNET_TFLOP_PER_VOLUME_128 = 2.340  # BASELINE.md section 2 (U-Net fwd+bwd, 128^3)
+# Learning rate of the benched step.  AdamW still runs its full sweep over parameters, gradients and moments (the same
+# kernels and bytes at any rate), but with 0 the weights stay put, so every warm-up and timed step computes from the same
+# weights and inputs.  At 1e-3 the kernels' order-dependent fp32 atomics grow through the Adam steps
+# into per-cent differences between two runs, and what the step computed could not be compared from run to run.
+BENCH_LR = 0.0
 
 
 def cpu_baseline(size, threads, batch=2, gpu_model_factory=None):
@@ -172,6 +183,49 @@ def timed_steps(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # all arrays of one --dump-outputs together
+DUMP_MAX_ELEMS = 1 << 22          # larger arrays are written as a seeded sample (the prediction at 128^3, batch 2 is whole)
+DUMP_FLAT_SAMPLE = 1 << 20        # elements sampled from the flat parameter / gradient buffers
+
+
+def _dump_array(t, cap, seed):
+    """float32 / float64 host copy of `t`, flattened to a seeded sample of `cap` elements if it is larger: indices drawn
+    with replacement from a CPU generator seeded by `seed` and sorted, so that two runs of the same shape pick the same ones."""
+    t = t.detach()
+    if t.numel() > cap:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    return t.to(dt).cpu().numpy()
+
+
+def dump_outputs(out_dir, losses, outs, opt):
+    """Writes what the last timed step handed its caller as <out_dir>/<name>.npy: the four loss terms of
+    train.forward_loss, the model outputs (prediction, the projection heads, the final projection) and seeded samples of
+    the parameters AFTER the optimizer step and of the step's gradients (the flat fp32 buffers of optim.FusedAdamW).
+    Arrays above DUMP_MAX_ELEMS are sampled; the cap halves until everything fits DUMP_BUDGET_BYTES.
+    Inputs and initial weights are seeded and the step runs at BENCH_LR = 0, so two runs of one build write the same
+    arrays up to the rounding of the kernels' fp32 atomics."""
+    import numpy as np
+    named = [(n, t) for n, t in zip(("loss_total", "loss_generative", "loss_pred_contrast", "loss_ds_contrast"), losses)]
+    pred, projected, final_proj = outs[0], outs[1], outs[2]
+    named += [("pred", pred), ("final_projection", final_proj)]
+    named += [(f"projected_{i}", t) for i, t in enumerate(projected)]
+    flat = [("params_sample", opt.flat_p), ("grads_sample", opt.flat_g)] if opt.flat_p is not None else []
+    cap = DUMP_MAX_ELEMS
+    while True:
+        arrays = {n: _dump_array(t, cap, seed=i) for i, (n, t) in enumerate(named)}
+        arrays.update({n: _dump_array(t, min(cap, DUMP_FLAT_SAMPLE), seed=100 + i) for i, (n, t) in enumerate(flat)})
+        if sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES:
+            break
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+    return sorted(arrays)
+
+
 def secondary_figures(args, dev, headline_ms, eager_ctx):
     """Driver-visible numbers beside the headline (N = 1 only; a few seconds each) -- see the module docstring."""
     import coma_unet_amd as cu
@@ -255,15 +309,22 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--batch", type=int, default=2, help="volumes per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (eager step, staged inputs, fp32, C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel rooflines, secondary figures, CPU baseline + "
+                         "parity, the data-parallel breakdown (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and parity")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="(--full) skip the per-kernel HIP-event timing")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the secondary figures (eager step, staged inputs, fp32, C5)")
     ap.add_argument("--no-graph", action="store_true", help="run the step eagerly even on one GPU")
     ap.add_argument("--dp", default=os.environ.get("COMA_DP", "torch"), choices=["torch", "capi", "capi-sharded"],
                     help="N > 1 gradient exchange: torch = torch.distributed (RCCL) all-reduce after the graph-replayed fwd+bwd; "
                          "capi = the C-ABI RCCL path (coma_allreduce_sum_f32 on a side stream, launched from the gradient sink "
                          "while backward runs, captured INSIDE the step graph); capi-sharded = reduce-scatter + AdamW on 1/N + all-gather")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -299,7 +360,7 @@ def main():
     if world > 1:
         broadcast_module(model)
     crit = cu.build_reference_criterion(dev)
-    opt = make_optimizer(model, 1e-3, pad_to=world if args.dp == "capi-sharded" else 1)
+    opt = make_optimizer(model, BENCH_LR, pad_to=world if args.dp == "capi-sharded" else 1)
 
     def make_reducer():
         if world == 1:
@@ -334,7 +395,7 @@ def main():
     if use_graph:
         try:
             step_fn = GraphedTrainStep(model, crit, opt, batch, warmup=max(args.warmup, 2), reducer=reducer)
-            run_step = lambda: step_fn()[0]
+            run_step = lambda: step_fn()
         except Exception as e:      # never lose the measurement to a capture problem: fall back to the eager step
             graph_note = f"graph capture failed ({type(e).__name__}: {e}); eager step used"
             print(graph_note, file=sys.stderr, flush=True)
@@ -345,8 +406,8 @@ def main():
     if not use_graph:
         for _ in range(args.warmup):
             train_step(model, crit, opt, batch, reducer)
-        run_step = lambda: train_step(model, crit, opt, batch, reducer)[0]
-        ops.KernelTimer.enabled = not args.no_kernel_timer
+        run_step = lambda: train_step(model, crit, opt, batch, reducer)
+        ops.KernelTimer.enabled = args.full and not args.no_kernel_timer
         ops.KernelTimer.records = []
     sync_all()
     t0 = time.perf_counter()
@@ -356,8 +417,12 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     ops.KernelTimer.enabled = False
+    last_losses, last_outs = last
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before anything below takes another step on these parameters
+        dumped = dump_outputs(args.dump_outputs, last_losses, last_outs, opt)
     timer_note = "HIP events around every conv launch of the timed steps"
-    if use_graph and not args.no_kernel_timer:
+    if args.full and use_graph and not args.no_kernel_timer:
         # kernels inside a graph replay cannot be bracketed individually: time the SAME kernels in two eager steps
         ops.KernelTimer.enabled = True
         ops.KernelTimer.records = []
@@ -372,6 +437,7 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if world > 1 and args.full:
         # how much of the step is the gradient exchange, and how much of the exchange is exposed:
         #   exchange_ms  one exchange of the whole flat gradient buffer with nothing beside it (the mode's own collectives)
         #   local_ms     the same step without any exchange (each rank alone; run AFTER the timed region: the replicas may drift)
@@ -417,7 +483,7 @@ def main():
                        "graph_overlap": getattr(reducer, "watch_probe", None)}
         except Exception as e:
             dp_info = {"mode": args.dp, "error": f"{type(e).__name__}: {e}"}
-    loss = float(last[0])
+    loss = float(last_losses[0])
 
     if rank == 0:
         vols = args.batch * world * args.steps
@@ -456,18 +522,19 @@ def main():
                        "params_M": round(sum(p.numel() for p in model.parameters()) / 1e6, 1)},
             "loss": round(loss, 4), "note": graph_note,
             "unet_tflops_per_s": round(step_ach, 2),
-            "roofline": roof, "roofline_mfma": roof_mfma, "roofline_hbm": roof_hbm, "roofline_thick_conv": roof_thick,
-            "conv_kernels": kernels,
             "zero_arena_mb": {str(k): round(a.peak / 2 ** 20, 1) for k, a in ops.ZeroArena._arenas.items()},
-            "data_parallel": dp_info,
+            "full": args.full, "dumped_outputs": dumped,
         }
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            line.update({"roofline": roof, "roofline_mfma": roof_mfma, "roofline_hbm": roof_hbm, "roofline_thick_conv": roof_thick,
+                         "conv_kernels": kernels, "data_parallel": dp_info})
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 line["secondary"] = secondary_figures(args, dev, elapsed / args.steps * 1e3,
                                                       (model, crit, opt, batch, step_fn if use_graph else None))
             except Exception as e:      # never lose the headline to a secondary measurement
                 line["secondary"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 threads = len(os.sched_getaffinity(0))
             except Exception:
@@ -488,7 +555,7 @@ def main():
                         line["secondary"][key] = {"error": f"{type(e).__name__}: {e}"}
             factory = lambda: (lambda mm: (mm.set_save_attn(None), mm)[1])(cu.build_model(volume_shape=S, compute_dtype=dt).to(dev))
             line["cpu_baseline"], line["parity"] = cpu_baseline(args.size, threads, args.batch, factory)
-        else:
+        elif args.full:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if world > 1:
