@@ -775,6 +775,7 @@ def test_fused_gate_block_matches_torch(C, dtype):
     ops, L = _ops()
     from coma_unet_amd.attn_unet_data_parallel import ObservableAttentionBlock
     from coma_unet_amd.layers import Config
+    from oracle.fp64_ref import gate_ref
     torch.manual_seed(C)
     Fi = C // 2
     B, dims = 2, (4, 6, 8)
@@ -792,14 +793,7 @@ def test_fused_gate_block_matches_torch(C, dtype):
     P = {k: v.detach().double().cpu().clone().requires_grad_(True) for k, v in blk.named_parameters()}
     gr, xr = gq.clone().requires_grad_(True), xq.clone().requires_grad_(True)
     rm = {n: [torch.zeros(c, dtype=torch.float64), torch.ones(c, dtype=torch.float64)] for n, c in (("W_g", Fi), ("W_x", Fi), ("psi", 1))}
-
-    def cbn(name, t):
-        y = F.conv3d(t, P[f"{name}.0.conv.weight"], P[f"{name}.0.conv.bias"])
-        return F.batch_norm(y, rm[name][0], rm[name][1], P[f"{name}.1.weight"], P[f"{name}.1.bias"], True, 0.1, 1e-5)
-
-    s_r = F.relu(cbn("W_g", gr) + cbn("W_x", xr))
-    psi_r = torch.sigmoid(cbn("psi", s_r))
-    att_r = xr * psi_r
+    att_r, psi_r = gate_ref(P, gr, xr, rm)
     ((att_r * gy).sum() + (xr * gy2).sum()).backward()          # (second consumer of x: a plain weighted sum)
     # ---- HIP
     dev = "cuda"
@@ -923,6 +917,9 @@ def test_tconv_halo_kernel_stats_and_accumulate(dims, dtype):
     (64, 32, (5, 7, 45), "fwd"), (128, 64, (4, 8, 32), "fwd"), (32, 64, (3, 5, 40), "dgrad"), (64, 128, (2, 8, 64), "dgrad"),
     # the 16-wide form (2 x 8 x 16 tiles, an M-tile = two x-rows): exact and ragged grids, many chunks, two output tiles
     (32, 32, (4, 16, 16), "fwd"), (64, 64, (5, 9, 20), "fwd"), (256, 32, (2, 8, 31), "fwd"), (32, 64, (3, 17, 16), "dgrad"),
+    # multi-tile runs: 720 ids over 128 blocks (6 ragged tiles per block, the tile-to-tile loop and statistics over many
+    # tiles), and 3 tiles per block on the data-gradient form
+    (32, 32, (48, 40, 96), "fwd"), (32, 32, (24, 40, 96), "dgrad"),
 ])
 def test_duo_kernel_matches_fp64_reference(case):
     """conv_mfma_duo_k (two 4-wave groups per CU alternating matrix and staging phases; the thick stride-1 layers):
