@@ -48,10 +48,17 @@ bool conv_mfma_wgrad_supported(const coma_conv_desc* d, const coma_tensor* x, co
 size_t conv_mfma_wgrad_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
                     size_t ws_bytes, hipStream_t s, int zeroed);
+// conv_split.hip (algo 4: fp32 tensors, two-term bf16 split on the bf16 matrix pipe)
+bool conv_split_fwd_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+int conv_split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                   hipStream_t s, double2* stats, int stats_inst, int* stats_chunks);
+bool conv_split_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed);
 
 extern "C" int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   if (d->algo == 1) return 1;
   if (conv_point1_ok(d, x, y)) return 1;            // one channel on a side: streaming dot / scale kernels (fp32 weights)
+  if (d->algo == 4 && conv_split_fwd_ok(d, x, y)) return 4;   // split: the thick stride-1 3^3 fp32 layers; every other problem as algo 0
   if (conv_mfma_supported(d, x, y)) return 2;       // bf16 tensors: MFMA wherever the shape allows
   if (conv_f32mfma_supported(d, x, y)) return 3;    // fp32 tensors: fp32 MFMA wherever the shape allows
   return 1;
@@ -87,6 +94,7 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
     return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, ws, ws_bytes, wz, accum);
   }
   COMA_CHECK(wk_dtype == COMA_F32, "conv_fwd: fp32 tensors need fp32 kernel-layout weights");
+  if (algo == 4) return conv_split_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr);
   if (algo == 3) return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, ws, ws_bytes, wz, accum);
   if (conv_point1_ok(d, x, y)) return conv_point1_fwd(d, x, (const float*)wk, bias, y, s);
   return conv_direct_fwd(d, x, (const float*)wk, bias, y, s);
@@ -94,6 +102,7 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
 
 extern "C" int coma_conv_wgrad_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   if (d->algo == 1 || conv_point1_ok(d, x, dy)) return 1;
+  if (d->algo == 4 && conv_split_wgrad_ok(d, x, dy)) return 4;
   if (!conv_mfma_wgrad_supported(d, x, dy)) return 1;
   return x->dtype == COMA_BF16 ? 2 : 3;
 }
@@ -108,10 +117,12 @@ extern "C" int coma_conv_fwd_norm_stats(const coma_conv_desc* d, const coma_tens
   COMA_CHECK(wk && sums, "conv_fwd_norm_stats: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const int algo_ = coma_conv_pick_algo(d, x, y);
-  if ((algo_ == 2 && wk_dtype == COMA_BF16) || (algo_ == 3 && wk_dtype == COMA_F32)) {
+  if ((algo_ == 2 && wk_dtype == COMA_BF16) || (algo_ >= 3 && wk_dtype == COMA_F32)) {
     int fused = 0;
     const int inst = mode == COMA_NORM_INSTANCE ? y->B : 0;      // (the kernels' group count; 0 = one BatchNorm group)
-    if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0)) return rc;
+    if (algo_ == 4) {
+      if (int rc = conv_split_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused)) return rc;
+    } else if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0)) return rc;
     if (fused) return 0;
   } else {
     if (int rc = coma_conv_fwd(d, x, wk, wk_dtype, bias, y, stream)) return rc;
@@ -145,6 +156,7 @@ extern "C" int coma_conv_wgrad(const coma_conv_desc* d, const coma_tensor* x, co
   }
   if (conv_point1_ok(d, x, dy)) return conv_point1_wgrad(d, x, dy, dwk, s, zeroed);
   const int algo = coma_conv_wgrad_algo(d, x, dy);
+  if (algo == 4) return conv_split_wgrad(d, x, dy, dwk, s, zeroed);
   if (algo >= 2) return conv_mfma_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   return conv_direct_wgrad(d, x, dy, dwk, s, zeroed);
 }

@@ -10,10 +10,8 @@
 // Replaces the cuDNN dispatches behind nn.Conv3d / nn.ConvTranspose3d forward and data-gradient
 // in the reference model (attn_unet_data_parallel.py; MONAI Convolution / CondConv call sites).
 #include "common.h"
+#include "conv_tiles.h"   // bf16x8_t / f32x16_t, stat_add, xcd_remap, tile_coords
 #include <type_traits>
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // 8 bf16 = one MFMA A/B fragment
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;  // 32x32 accumulator fragment
 
 // ---- element type of the activations / kernel-layout weights: bf16 (v_mfma_f32_32x32x16_bf16) or fp32
 // (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, 1/16 of the bf16 rate -- the "fp32 mode" of the model,
@@ -36,18 +34,6 @@ __device__ __forceinline__ f32x16_t mma_piece(const uint4& a, const uint4& b, f3
   return acc;
 }
 
-// fused norm statistics: a block ADDS its {sum, sumsq} of one (group, channel) to the caller's zeroed fp64 record
-// rec[COMA_STAT_REPLICAS][G][N][2] (replica stride rounded up to a 64-byte line) with global_atomic_add_f64; every consumer
-// sums the replicas and derives mean / rstd itself (norm.hip, NormStat).  Replicas: float atomics execute at the memory
-// side at ~25 ns per request to one 64-byte line, so a few hundred blocks adding to ONE record would queue for
-// microseconds at the end of the kernel; spread over 8 replicas by block index the queue per line is 8x shorter.
-__device__ __forceinline__ void stat_add(double2* rec, int G, int N, int g, int n, double a, double c) {
-  const long rs = ((long)G * N * 2 + 7) & ~7L;
-  double* q = reinterpret_cast<double*>(rec) + (long)(blockIdx.x & (COMA_STAT_REPLICAS - 1)) * rs + ((long)g * N + n) * 2;
-  unsafeAtomicAdd(q, a);
-  unsafeAtomicAdd(q + 1, c);
-}
-
 struct GatherP {
   const void* x; int ldx; long sbx; int Di, Hi, Wi, C;
   void* y; int ldy; long sby; int Do, Ho, Wo, N;
@@ -62,27 +48,6 @@ struct GatherP {
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return (row << 2) | (chunk ^ ((row >> 2) & 3)); }  // 16-B slot index
-
-// blockIdx -> work-item remap: the dispatcher deals consecutive blocks round-robin over the 8 XCDs
-// (each with a private 4 MiB L2); give every XCD one CONTIGUOUS range of the work so that
-// neighbouring tiles (which share halo voxels) hit in the same L2.  Bijective for any grid size.
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-// tile id -> (tix, tiy, tiz): x slowest, then blocks of 8 z-tiles, then y, z-in-block fastest, so
-// the ~64 tiles an XCD works on at once form an 8(y) x 8(z) patch (halo overlap 3.2x -> ~1.3x).
-// ids run over ntx * ceil(ntz/8) * nty * 8; returns false for the padding ids (tiz >= ntz).
-__device__ __forceinline__ bool tile_coords(int id, int ntx, int nty, int ntz, int& tix, int& tiy, int& tiz) {
-  const int ntzb = (ntz + 7) >> 3;
-  const int zin = id & 7;
-  int t = id >> 3;
-  tiy = t % nty; t /= nty;
-  const int tzb = t % ntzb;
-  tix = t / ntzb;
-  tiz = tzb * 8 + zin;
-  return tiz < ntz && tix < ntx;
-}
 
 // MODE 0: in = m*stride - pad + tap  (all taps; `flip` mirrors the weight tap index)
 // MODE 1: stride-2 transposed gather, one output-parity class per blockIdx.y slice
@@ -4668,4 +4633,9 @@ int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_te
 #undef WL
   COMA_LAUNCH_CHECK();
   return 0;
+}
+
+// the fp32 problems conv_mfma_halo<float> runs on conv_mfma_halo2_k<2, 16, 1, 1, float>: what conv_split.hip takes under algo 4
+bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return conv_f32mfma_supported(d, x, y) && !thin16f_ok(d, x, y) && f32_halo_ok(d, x, y) && x->W >= 32;
 }

@@ -1,0 +1,538 @@
+// Split-bf16 convolution kernels for gfx950: fp32 tensors and fp32 kernel-layout weights, products on
+// v_mfma_f32_32x32x16_bf16 (coma_conv_desc.algo = 4).
+//
+// Every fp32 operand a is split when it is STAGED into LDS (once per element, not once per use) into two bf16 values
+//     a_hi = bf16(a),   a_lo = bf16(a - float(a_hi))            (both round-to-nearest-even)
+// and a product is formed from three MFMAs into one fp32 accumulator
+//     a * b  ~=  a_hi * b_hi  +  a_hi * b_lo  +  a_lo * b_hi.
+// |a - a_hi - a_lo| <= 2^-16 |a| and |a_lo| <= 2^-8 (1 + 2^-8) |a|, so the dropped terms (a_lo b_lo and the two
+// residuals) are below 3.03 * 2^-16 |a||b| < 2^-14 |a||b| per product; a product of two bf16 values is exact in fp32.
+// Matrix-pipe cost of 16 channels of K: 3 x 32 cycles, against 8 x 64 cycles of v_mfma_f32_32x32x2_f32.
+// Non-finite inputs do not split (inf - inf): an infinite operand yields NaN where the exact kernels yield inf.
+//
+//   conv_split_halo_k  -- stride-1 3x3x3 forward / data gradient (the problems of conv_mfma_halo2_k<2, 16, 1, 1, float>)
+//   conv_split_wgrad_k -- stride-1 3x3x3 weight gradient          (the problems of conv_f32_wgrad16_k<1, 0>)
+#include "common.h"
+#include "conv_tiles.h"
+
+typedef __attribute__((ext_vector_type(4))) short s4_t;
+typedef __attribute__((address_space(3))) s4_t lds_s4_t;
+
+// conv_mfma.hip: the fp32 problems its halo-tiled kernel takes at W >= 32
+bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// 4 fp32 (one 16-byte staging piece) -> 4 bf16 hi + 4 bf16 lo
+__device__ __forceinline__ void split4(const uint4& v, uint2& hi, uint2& lo) {
+  const float f[4] = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
+  bf16_t h[4], l[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h[j] = static_cast<bf16_t>(f[j]);
+    l[j] = static_cast<bf16_t>(f[j] - static_cast<float>(h[j]));
+  }
+  hi = *reinterpret_cast<const uint2*>(h);
+  lo = *reinterpret_cast<const uint2*>(l);
+}
+
+__device__ __forceinline__ f32x16_t mma3(const uint4& a_hi, const uint4& a_lo, const uint4& b_hi, const uint4& b_lo, f32x16_t acc) {
+  const bf16x8_t ah = *reinterpret_cast<const bf16x8_t*>(&a_hi), al = *reinterpret_cast<const bf16x8_t*>(&a_lo);
+  const bf16x8_t bh = *reinterpret_cast<const bf16x8_t*>(&b_hi), bl = *reinterpret_cast<const bf16x8_t*>(&b_lo);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);     // (small terms first)
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+  return acc;
+}
+
+// =====================================================================================
+// conv_split_halo_k -- the structure of conv_mfma_halo2_k<2, 16, 1, 1, float>: one 4-wave block per CU walks a run of
+// 2 x 4 x 32-voxel tiles; per (tile, 16-channel chunk) the 4 x 6 x 34 halo and the chunk's 27 x 32 weight rows sit in LDS,
+// the next chunk's pieces are fetched by buffer loads issued between the MFMAs.  An LDS row holds the SAME 64 bytes the
+// fp32 kernel keeps (16 fp32 channels), now as [16 bf16 hi][16 bf16 lo]; 80-byte row pitch, so the 16-byte fragment reads
+// of 16 consecutive rows land on 16 distinct slots.  A wave's two M-tiles are y-neighbours: for a fixed (kz, kx) their
+// three ky taps read four halo rows, so a (kz, kx) group is 8 + 6 fragment reads for 18 MFMAs.
+// The MFMA is (weights x voxels): a lane holds 4 x 4 consecutive output channels of one voxel (16-byte fp32 stores).
+// =====================================================================================
+struct SplitHaloP {
+  const float* x; int ldx; long sbx; int D, H, W, C;
+  float* y; int ldy; long sby; int N;
+  const float* w; long wsb;
+  const float* bias; int bsb;
+  int flip;
+  int ntx, nty, ntz, ids_total, ids_per_block;
+  unsigned xbytes, wbytes;   // bytes of one sample of x / of one weight set (buffer descriptors: out-of-range pieces read as zero)
+  int st16;                  // output rows allow aligned 16-byte (4-channel) stores
+  double2* stats;            // optional fused norm statistics record (stat_add)
+  int stats_inst;            // B: groups = the B samples (InstanceNorm), 0: one group (BatchNorm)
+};
+
+__global__ __launch_bounds__(256, 1) void conv_split_halo_k(SplitHaloP p) {
+  constexpr int CK = 16, TX = 32, TY = 4, TZ = 2, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HV = HX * HY * HZ;
+  constexpr int P = 80;                                  // LDS row pitch (bytes)
+  constexpr int HP = HV * 4, HIT = (HP + 255) / 256;     // 16-byte fp32 pieces of a halo chunk, per-thread iterations
+  constexpr int WP = 27 * 32 * 4, WIT = (WP + 255) / 256;
+  static_assert(WIT + HIT <= 27, "one prefetch piece per tap");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Hl = smem;                                       // [HV][80]
+  char* Wl = smem + HV * P;                              // [27 * 32][80]
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int b = blockIdx.z, n0 = blockIdx.y * 32;
+  const int fr = lane & 31, fh = lane >> 5;
+  const float* xb = p.x + (long)b * p.sbx;
+  const float* wb = p.w + (long)b * p.wsb;
+  float* yb = p.y + (long)b * p.sby;
+  const int nchunks = p.C / CK;
+
+  // ---- staging descriptors (tile independent) ----
+  int h_roff[HIT], h_lds[HIT], h_z[HIT], h_y[HIT], h_x[HIT];
+#pragma unroll
+  for (int it = 0; it < HIT; ++it) {
+    const int piece = tid + 256 * it;
+    const int row = piece >> 2, ch = piece & 3;
+    const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+    h_z[it] = piece < HP ? hz : (1 << 20); h_y[it] = hy; h_x[it] = hx;
+    h_roff[it] = ((hz * p.H + hy) * p.W + hx) * p.ldx + ch * 4;
+    h_lds[it] = row * P + ch * 8;                        // hi half; lo at + 32
+  }
+  constexpr unsigned OOB = 0x7fff0000u;
+  int w_lds[WIT];
+  unsigned w_boff[WIT];
+#pragma unroll
+  for (int it = 0; it < WIT; ++it) {
+    const int piece = tid + 256 * it;
+    const int ch = piece & 3, n = (piece >> 2) & 31, t = piece >> 7;
+    const int wt = p.flip ? 26 - t : t;
+    w_boff[it] = (piece < WP && n0 + n < p.N) ? (unsigned)(((wt * p.N + n0 + n) * p.C + ch * 4) * 4) : OOB;   // + chunk offset at load time
+    w_lds[it] = (t * 32 + n) * P + ch * 8;
+  }
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.xbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, p.wbytes, 0x00020000);
+  // fragment read bases: the wave's two M-tiles are rows y, y + 1 of one z plane
+  const int a_base = ((((wid * 2) >> 2) * HY + ((wid * 2) & 3)) * HX + fr) * P + fh * 16;
+  const int w_base = fr * P + fh * 16;
+
+  uint4 hreg[HIT], wreg[WIT];
+  auto load_halo = [&](int z0, int y0, int x0, int c0) {
+    const int zb = z0 - 1, yb0 = y0 - 1, xb0 = x0 - 1;
+    const unsigned org_b = (unsigned)((((long)(zb * p.H + yb0) * p.W + xb0) * p.ldx + c0) * 4L);   // (mod 2^32: a valid piece's sum is its true offset)
+#pragma unroll
+    for (int it = 0; it < HIT; ++it) {
+      const bool ok = (unsigned)(zb + h_z[it]) < (unsigned)p.D && (unsigned)(yb0 + h_y[it]) < (unsigned)p.H &&
+                      (unsigned)(xb0 + h_x[it]) < (unsigned)p.W;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? org_b + (unsigned)h_roff[it] * 4u : OOB, 0, 0);
+      hreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
+  auto load_w = [&](int c0) {
+#pragma unroll
+    for (int it = 0; it < WIT; ++it) {
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_boff[it], c0 * 4, 0);
+      wreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
+  // the split happens here: one conversion per staged element, two 8-byte LDS stores per piece
+  auto store_halo = [&]() {
+#pragma unroll
+    for (int it = 0; it < HIT; ++it)
+      if (tid + 256 * it < HP) {
+        uint2 hi, lo;
+        split4(hreg[it], hi, lo);
+        *reinterpret_cast<uint2*>(Hl + h_lds[it]) = hi;
+        *reinterpret_cast<uint2*>(Hl + h_lds[it] + 32) = lo;
+      }
+  };
+  auto store_w = [&]() {
+#pragma unroll
+    for (int it = 0; it < WIT; ++it)
+      if (tid + 256 * it < WP) {
+        uint2 hi, lo;
+        split4(wreg[it], hi, lo);
+        *reinterpret_cast<uint2*>(Wl + w_lds[it]) = hi;
+        *reinterpret_cast<uint2*>(Wl + w_lds[it] + 32) = lo;
+      }
+  };
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  if (id >= id_end) return;      // padding ids only: nothing to store, nothing to add to the statistics record
+  load_halo(tiz * TZ, tiy * TY, tix * TX, 0);
+  load_w(0);
+
+  const bool do_stats = p.stats != nullptr;
+  float bv[4][4];
+  float st_s[4][4], st_q[4][4];     // fused norm statistics of this lane's 16 channels (stored values)
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = n0 + 8 * g4 + 4 * fh + q;
+      bv[g4][q] = (p.bias && n < p.N) ? p.bias[b * p.bsb + n] : 0.f;
+      st_s[g4][q] = 0.f; st_q[g4][q] = 0.f;
+    }
+
+  while (id < id_end) {
+    const int x0 = tix * TX, y0 = tiy * TY, z0 = tiz * TZ;
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+
+    f32x16_t acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+
+    for (int cc = 0; cc < nchunks; ++cc) {
+      __syncthreads();                       // all waves finished reading the previous halo / weights
+      store_halo();
+      store_w();
+      __syncthreads();
+      // prefetch while this chunk computes: the next chunk of this tile, or chunk 0 of the next tile; one piece per tap
+      // inside the MFMA loop, through descriptors whose range is zero when there is nothing to prefetch
+      const bool same_tile = cc + 1 < nchunks;
+      const bool pref = same_tile || has_next;
+      const int pz = same_tile ? z0 : ntiz * TZ, py = same_tile ? y0 : ntiy * TY, px = same_tile ? x0 : ntix * TX;
+      const int pc0 = same_tile ? cc * CK + CK : 0;
+      const __amdgpu_buffer_rsrc_t rs_xp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, pref ? p.xbytes : 0, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs_wp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, pref ? p.wbytes : 0, 0x00020000);
+      const unsigned porg_b = (unsigned)((((long)((pz - 1) * p.H + (py - 1)) * p.W + (px - 1)) * p.ldx + pc0) * 4L);
+      auto pref_piece = [&](int t) __attribute__((always_inline)) {
+        if (t < WIT) {
+          const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_wp, w_boff[t], pc0 * 4, 0);
+          wreg[t] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        const int it = t - WIT;
+        if (it >= 0 && it < HIT) {
+          const bool ok = (unsigned)(pz - 1 + h_z[it]) < (unsigned)p.D && (unsigned)(py - 1 + h_y[it]) < (unsigned)p.H &&
+                          (unsigned)(px - 1 + h_x[it]) < (unsigned)p.W;
+          const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_xp, ok ? porg_b + (unsigned)h_roff[it] * 4u : OOB, 0, 0);
+          hreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+      };
+      // fragments one (kz, kx) group ahead, in a second register set: [.][.][0] = hi, [.][.][1] = lo
+      uint4 wg[2][3][2], xr[2][4][2];
+      auto rdg = [&](int g, int bf) __attribute__((always_inline)) {
+        const int kz = g / 3, kx = g % 3;
+        const int toff = (kz * HY * HX + kx) * P;
+#pragma unroll
+        for (int hl = 0; hl < 2; ++hl) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) xr[bf][r][hl] = *reinterpret_cast<const uint4*>(Hl + a_base + toff + r * HX * P + hl * 32);
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+            wg[bf][ky][hl] = *reinterpret_cast<const uint4*>(Wl + w_base + (kz * 9 + ky * 3 + kx) * 32 * P + hl * 32);
+        }
+      };
+      rdg(0, 0);
+#pragma unroll
+      for (int g = 0; g < 9; ++g) {
+        if (g + 1 < 9) rdg(g + 1, (g + 1) & 1);
+        pref_piece(3 * g); pref_piece(3 * g + 1); pref_piece(3 * g + 2);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+            acc[i] = mma3(wg[g & 1][ky][0], wg[g & 1][ky][1], xr[g & 1][i + ky][0], xr[g & 1][i + ky][1], acc[i]);
+        // 18 MFMAs; the next group's 14 fragment reads and this group's 3 prefetch pieces go BETWEEN them
+#define COMA_SGB(mfma, ds, valu, vmem)                                   \
+        __builtin_amdgcn_sched_group_barrier(0x008, mfma, 0);            \
+        if (ds) __builtin_amdgcn_sched_group_barrier(0x100, ds, 0);      \
+        if (valu) __builtin_amdgcn_sched_group_barrier(0x006, valu, 0);  \
+        if (vmem) __builtin_amdgcn_sched_group_barrier(0x020, vmem, 0);
+        COMA_SGB(1, 1, 4, 0) COMA_SGB(1, 1, 4, 1) COMA_SGB(1, 1, 4, 0) COMA_SGB(1, 1, 4, 0) COMA_SGB(1, 1, 4, 1) COMA_SGB(1, 1, 4, 0)
+        COMA_SGB(1, 1, 4, 0) COMA_SGB(1, 1, 4, 1) COMA_SGB(1, 1, 2, 0) COMA_SGB(1, 1, 2, 0) COMA_SGB(1, 1, 2, 0) COMA_SGB(1, 1, 2, 0)
+        COMA_SGB(1, 1, 0, 0) COMA_SGB(1, 1, 0, 0) COMA_SGB(1, 0, 0, 0) COMA_SGB(1, 0, 0, 0) COMA_SGB(1, 0, 0, 0) COMA_SGB(1, 0, 0, 0)
+#undef COMA_SGB
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // ---- epilogue: lane = one voxel, 4 groups of 4 consecutive channels, one 16-byte store each ----
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int j = wid * 2 + i;
+      const int gz = z0 + (j >> 2), gy = y0 + (j & 3), gx = x0 + fr;
+      const bool valid = gz < p.D && gy < p.H && gx < p.W;
+      float* dst = yb + ((long)(gz * p.H + gy) * p.W + gx) * p.ldy + n0 + 4 * fh;
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        if (n0 + 8 * g4 >= p.N) continue;            // (wave-uniform)
+        float o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          o[q] = acc[i][g4 * 4 + q] + bv[g4][q];
+          if (do_stats) { const float r = valid ? o[q] : 0.f; st_s[g4][q] += r; st_q[g4][q] = fmaf(r, r, st_q[g4][q]); }
+        }
+        if (valid) {
+          if (p.st16 && n0 + 8 * g4 + 4 * fh + 3 < p.N) *reinterpret_cast<float4*>(dst + 8 * g4) = make_float4(o[0], o[1], o[2], o[3]);
+          else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if (n0 + 8 * g4 + 4 * fh + q < p.N) dst[8 * g4 + q] = o[q];
+          }
+        }
+      }
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+  // ---- fused statistics: lanes -> wave (butterfly over the 32 voxel lanes) -> block (LDS) -> record ----
+  if (do_stats) {
+    __syncthreads();                                  // LDS images are dead; reuse the front as a [4 waves][32 ch][2] table
+    float* red = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float a = st_s[g4][q], c = st_q[g4][q];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+        if (fr == 0) { red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2] = a; red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2 + 1] = c; }
+      }
+    __syncthreads();
+    if (tid < 32 && n0 + tid < p.N) {
+      double a = 0.0, c = 0.0;
+      for (int w = 0; w < 4; ++w) { a += (double)red[(w * 32 + tid) * 2]; c += (double)red[(w * 32 + tid) * 2 + 1]; }
+      const int g = p.stats_inst ? b : 0;
+      stat_add(p.stats, p.stats_inst ? p.stats_inst : 1, p.N, g, n0 + tid, a, c);
+    }
+  }
+}
+
+bool conv_split_fwd_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return conv_f32_halo2_problem(d, x, y);
+}
+
+int conv_split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                   hipStream_t s, double2* stats, int stats_inst, int* stats_chunks) {
+  COMA_CHECK(conv_split_fwd_ok(d, x, y), "conv_split: problem not in the split kernel's scope");
+  COMA_CHECK(aligned16(x->data) && aligned16(wk), "conv_split: operands must allow 16-byte channel pieces (aligned)");
+  SplitHaloP q;
+  q.x = (const float*)x->data; q.ldx = (int)x->ld; q.sbx = x->sb; q.D = x->D; q.H = x->H; q.W = x->W; q.C = x->C;
+  q.y = (float*)y->data; q.ldy = (int)y->ld; q.sby = y->sb; q.N = y->C;
+  q.w = (const float*)wk; q.wsb = d->per_sample_w ? 27L * y->C * x->C : 0;
+  q.bias = bias; q.bsb = d->per_sample_w ? y->C : 0;
+  q.flip = d->form == 1;
+  {   // descriptor ranges (one sample / one weight set), capped below the out-of-range marker 0x7fff0000
+    const unsigned long long xb_ = (unsigned long long)t_vox(x) * x->ld * 4, wb_ = 27ull * y->C * x->C * 4;
+    COMA_CHECK(wb_ < 0x7fff0000ull, "conv_split: weight set too large for 32-bit buffer offsets");
+    q.xbytes = (unsigned)(xb_ < 0x7fff0000ull ? xb_ : 0x7fff0000ull);
+    q.wbytes = (unsigned)wb_;
+  }
+  q.st16 = y->ld % 4 == 0 && y->sb % 4 == 0 && aligned16(y->data);
+  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
+  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
+  const int nblk_n = (q.N + 31) / 32;
+  int gx = 256 / (nblk_n * x->B);                      // one block per CU, one round
+  if (gx < 1) gx = 1;
+  if (gx > q.ids_total) gx = q.ids_total;
+  q.ids_per_block = (q.ids_total + gx - 1) / gx;
+  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  q.stats = nullptr; q.stats_inst = stats_inst;
+  if (stats) { q.stats = stats; *stats_chunks = 1; }
+  const size_t lds = (size_t)(34 * 6 * 4 + 27 * 32) * 80;
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_halo_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+  coma_set_kernel_tag("conv_split_halo_k");
+  hipLaunchKernelGGL(conv_split_halo_k, dim3((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B), dim3(256), lds, s, q);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================
+// conv_split_wgrad_k -- dwk[b][tap][n][c] += sum_m dy[m][n] * x[m + tap - 1][c], the reduction index is the voxel.
+// The frame of conv_f32_wgrad16_k<1, 0> (a block owns a 32 x 32 (n, c) weight tile and a run of 2 x 4 x 32-voxel tiles;
+// the dy tile and the 4 x 6 x 34 x halo are staged by buffer loads, the next tile's 34 pieces per thread in flight while
+// this one computes) with the MFMA body of conv_mfma_wgrad_k<1, 1, 0>: both operands are [voxel][32 channels] bf16 images
+// (64-byte rows) read transposed with ds_read_b64_tr_b16, the 27 taps are dealt to the 4 waves (7, 7, 7, 6) whose 32 x 32
+// fp32 accumulators stay in registers over the block's tiles and merge into dwk with fp32 atomics at the end.
+// Each image exists twice (hi, lo): together the bytes of the fp32 images of conv_f32_wgrad16_k (134 KB).
+// =====================================================================================
+struct SplitWgradP {
+  const float* dy; int ldd; long sbd;       // dense operand, N channels
+  const float* x; int ldg; long sbg;        // gathered operand, C channels (same grid: stride 1, pad 1)
+  int D, H, W, N, C;
+  unsigned dbytes, gbytes;
+  int ntx, nty, ntz, ids_total, ids_per_block, cblocks;
+  float* dwk; long wsb;
+};
+
+__global__ __launch_bounds__(256, 1) void conv_split_wgrad_k(SplitWgradP p) {
+  constexpr int TX = 32, TY = 4, TZ = 2, TM = TX * TY * TZ;
+  constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HV = HX * HY * HZ;
+  constexpr int PR = 64;                                // LDS row pitch (bytes): 32 bf16 channels
+  constexpr int HIT = (HV * 8 + 255) / 256, DIT = TM * 8 / 256, NIT = HIT + DIT;      // 16-byte fp32 pieces per thread
+  constexpr int MAXT = 7;                               // taps per wave
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Gh = smem;                                      // [HV][64] x hi
+  char* Gl = Gh + HV * PR;                              //          x lo
+  char* Dh = Gl + HV * PR;                              // [TM][64] dy hi
+  char* Dl = Dh + TM * PR;                              //          dy lo
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z;
+  const int n0 = (blockIdx.y / p.cblocks) * 32, c0 = (blockIdx.y % p.cblocks) * 32;
+  const float* dnb = p.dy + (long)b * p.sbd + n0;
+  const float* gab = p.x + (long)b * p.sbg + c0;
+  const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, p.gbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, p.dbytes, 0x00020000);
+  constexpr unsigned OOB = 0x7fff0000u;
+
+  // staging: piece = tid + 256 it -> (row = piece >> 3, 4-channel piece = tid & 7); positions relative to the tile origin - 1.
+  // A piece past the tensor's channels (partial 32-channel block) reads as zero: it never touches the neighbouring slice.
+  const int chq = (tid & 7) * 4;
+  const unsigned choff = (unsigned)(chq * 4);
+  const bool ch_g = c0 + chq < p.C, ch_d = n0 + chq < p.N;
+  int s_pos[NIT];                                       // packed z | y << 4 | x << 8
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (it < HIT) {
+      const int row = (tid + 256 * it) >> 3;
+      const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+      s_pos[it] = row < HV ? (hz | (hy << 4) | (hx << 8)) : (15 | (15 << 4) | (1023 << 8));
+    } else {
+      const int row = (tid + 256 * (it - HIT)) >> 3;
+      s_pos[it] = ((row / (TY * 32)) + 1) | ((((row >> 5) % TY) + 1) << 4) | (((row & 31) + 1) << 8);
+    }
+  }
+  uint4 sreg[NIT];
+  auto issue_all = [&](int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rg, const __amdgpu_buffer_rsrc_t& rd) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int gz = z0 - 1 + (s_pos[it] & 15), gy = y0 - 1 + ((s_pos[it] >> 4) & 15), gx = x0 - 1 + (s_pos[it] >> 8);
+      const bool ok = (unsigned)gz < (unsigned)p.D && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W && (it < HIT ? ch_g : ch_d);
+      const unsigned off = (unsigned)(((gz * p.H + gy) * p.W + gx) * (it < HIT ? p.ldg : p.ldd)) * 4u + choff;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(it < HIT ? rg : rd, ok ? off : OOB, 0, 0);
+      sreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
+  auto store_tile = [&]() __attribute__((always_inline)) {      // the split: one conversion per staged element
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      uint2 hi, lo;
+      split4(sreg[it], hi, lo);
+      if (it < HIT) {
+        const int piece = tid + 256 * it;
+        if ((piece >> 3) < HV) { *reinterpret_cast<uint2*>(Gh + piece * 8) = hi; *reinterpret_cast<uint2*>(Gl + piece * 8) = lo; }
+      } else {
+        const int piece = tid + 256 * (it - HIT);
+        *reinterpret_cast<uint2*>(Dh + piece * 8) = hi; *reinterpret_cast<uint2*>(Dl + piece * 8) = lo;
+      }
+    }
+  };
+
+  f32x16_t acc[MAXT];
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+  // per-wave tap list (wave-uniform): tap = wid + 4 t; byte offset of the tap's shift in the halo image
+  int toff_w[MAXT];
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) {
+    const int tap = wid + 4 * t;
+    const int kx = tap % 3, ky = (tap / 3) % 3, kz = tap / 9;
+    toff_w[t] = __builtin_amdgcn_readfirstlane(((kz * HY + ky) * HX + kx) * PR);
+  }
+  const bool last_tap = wid + 4 * (MAXT - 1) < 27;      // (wave 3 has six taps)
+  // lane roles of the transposed reads (as conv_mfma_wgrad_k): a 16-lane group covers 4 voxels x 16 channels per read
+  const int g16 = lane >> 4, li = lane & 15, q4 = li >> 2, pp = li & 3;
+  const int chan_b = ((g16 & 1) * 16 + 4 * pp) * 2;     // byte offset of this lane's 4 channels in the 32-channel row
+  const int vrow = 8 * (g16 >> 1) + q4;                 // voxel (within a 16-voxel K step) whose row this lane addresses
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  if (id >= id_end) return;
+  issue_all(tiz * TZ, tiy * TY, tix * TX, rs_g, rs_d);
+  while (id < id_end) {
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+    const __amdgpu_buffer_rsrc_t rn_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, has_next ? p.gbytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, has_next ? p.dbytes : 0, 0x00020000);
+    __syncthreads();
+    store_tile();
+    __syncthreads();
+    issue_all(ntiz * TZ, ntiy * TY, ntix * TX, rn_g, rn_d);
+    // 16 K steps of 16 voxels: step ks = half an x row of the tile
+#pragma unroll 2
+    for (int ks = 0; ks < TM / 16; ++ks) {
+      const int r = ks >> 1, xh = (ks & 1) * 16 + vrow;                      // dense row (z, y) of the tile, x within it
+      const int d1 = (r * 32 + xh) * PR + chan_b;
+      const int g1 = (((r / TY) * HY + (r % TY)) * HX + xh) * PR + chan_b;   // the same voxel in the halo image, tap (0, 0, 0)
+      auto frag = [&](const char* base) __attribute__((always_inline)) -> uint4 {
+        const s4_t u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base));
+        const s4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base + 4 * PR));
+        const bf16x8_t f = (bf16x8_t){u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+        return *reinterpret_cast<const uint4*>(&f);
+      };
+      const uint4 dh = frag(Dh + d1), dl = frag(Dl + d1);
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t) {
+        if (t < MAXT - 1 || last_tap) {
+          const uint4 gh = frag(Gh + g1 + toff_w[t]), gl = frag(Gl + g1 + toff_w[t]);
+          acc[t] = mma3(dh, dl, gh, gl, acc[t]);
+        }
+      }
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+  // ---- merge into dwk[b][tap][n][c]: MFMA rows = n (A = dy), columns = c (B = x) ----
+  float* wout = p.dwk + (long)b * p.wsb;
+  const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) {
+    const int tap = wid + 4 * t;
+    if (tap < 27) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int n = n0 + (e & 3) + 8 * (e >> 2) + 4 * fh, c = c0 + fr;
+        if (n < p.N && c < p.C) atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, acc[t][e]);
+      }
+    }
+  }
+}
+
+// the problems conv_f32_wgrad16_k<1, 0> takes, plus partial 32-channel blocks (C, N multiples of 16)
+bool conv_split_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  return d->ksize == 3 && d->form == 0 && d->stride == 1 && d->pad == 1 && x->dtype == COMA_F32 && dy->dtype == COMA_F32 &&
+         t_same_grid(x, dy) && x->W >= 32 && x->C >= 32 && dy->C >= 32 && x->C % 16 == 0 && dy->C % 16 == 0 &&
+         x->ld % 4 == 0 && x->sb % 4 == 0 && dy->ld % 4 == 0 && dy->sb % 4 == 0 &&
+         (!x->data || aligned16(x->data)) && (!dy->data || aligned16(dy->data)) &&
+         (unsigned long long)t_vox(x) * x->ld * 4 < 0x7fff0000ull && (unsigned long long)t_vox(dy) * dy->ld * 4 < 0x7fff0000ull;
+}
+
+int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
+  COMA_CHECK(conv_split_wgrad_ok(d, x, dy), "conv_split_wgrad: problem not in the split kernel's scope");
+  SplitWgradP q;
+  q.dy = (const float*)dy->data; q.ldd = (int)dy->ld; q.sbd = dy->sb;
+  q.x = (const float*)x->data; q.ldg = (int)x->ld; q.sbg = x->sb;
+  q.D = x->D; q.H = x->H; q.W = x->W; q.N = dy->C; q.C = x->C;
+  // (descriptor ranges are measured from the block's channel offset; the voxel and channel tests keep every piece inside)
+  q.dbytes = (unsigned)((unsigned long long)t_vox(dy) * dy->ld * 4);
+  q.gbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
+  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
+  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
+  q.cblocks = (q.C + 31) / 32;
+  const int pairs = q.cblocks * ((q.N + 31) / 32);
+  int gx = 256 / (pairs * x->B);                       // one block per CU, one round: a second round repeats the atomic merge
+  if (gx < 1) gx = 1;
+  if (gx > q.ids_total) gx = q.ids_total;
+  q.ids_per_block = (q.ids_total + gx - 1) / gx;
+  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
+  q.wsb = d->per_sample_w ? wsz1 : 0;
+  q.dwk = dwk;
+  if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const size_t lds = (size_t)2 * (34 * 6 * 4 + 256) * 64;
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_wgrad_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+  coma_set_kernel_tag("conv_split_wgrad_k");
+  hipLaunchKernelGGL(conv_split_wgrad_k, dim3((unsigned)gx, (unsigned)pairs, (unsigned)x->B), dim3(256), lds, s, q);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}

@@ -94,7 +94,7 @@ def conv_class(algo_name, cin, cout):
     return "mfma-thick" if min(cin, cout) >= 32 else "mfma-thin"
 
 
-_ALGO_NAMES = {1: "direct", 2: "mfma", 3: "mfma-f32"}
+_ALGO_NAMES = {1: "direct", 2: "mfma", 3: "mfma-f32", 4: "mfma-split"}   # 4: fp32 tensors, two-term bf16 split (csrc/conv_split.hip)
 
 
 def _new(shape, dtype, device):

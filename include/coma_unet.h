@@ -90,7 +90,12 @@ typedef struct coma_conv_desc {
   int32_t per_sample_w;   /* 1: wk/bias have a leading B dim (CondConv) */
   int32_t algo;           /* 0 auto: MFMA wherever the shape allows (bf16 tensors: v_mfma_f32_32x32x16_bf16; fp32 tensors:
                              v_mfma_f32_32x32x2_f32, exact fp32), otherwise the direct kernels;
-                             1 force the direct VALU fp32 kernels; 2 = 0 (kept for callers of ABI 1) */
+                             1 force the direct VALU fp32 kernels; 2 = 0 (kept for callers of ABI 1);
+                             4 split: fp32 tensors and fp32 kernel-layout weights, but the thick stride-1 3x3x3 layers at
+                             W >= 32 (forward, data gradient, weight gradient) form every product from a two-term bf16
+                             split of both operands on v_mfma_f32_32x32x16_bf16 (three MFMAs, fp32 accumulation: error
+                             below 2^-14 |a||b| per product); coma_conv_pick_algo / coma_conv_wgrad_algo answer 4 there.
+                             Every other problem, and bf16 tensors, resolve exactly as algo 0 does. */
 } coma_conv_desc;
 
 int         coma_abi_version(void);
@@ -132,8 +137,9 @@ int coma_routing_bwd(const float* cov, int32_t B, int32_t NC, const float* r, in
                      float* dWr, float* dbr, float* dbias_e, void* stream);
 
 /* ---- convolution (nn.Conv3d / nn.ConvTranspose3d and their data-gradients) ---- */
-/* which kernel family algo==0 resolves to for this problem: 1 direct (wants fp32 wk), 2 bf16 MFMA
- * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk).  The host prepares the kernel-layout
+/* which kernel family d->algo resolves to for this problem: 1 direct (wants fp32 wk), 2 bf16 MFMA
+ * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk), 4 split-bf16 MFMA (algo 4 only; fp32
+ * tensors, wants fp32 wk: the split is done inside the library).  The host prepares the kernel-layout
  * weights accordingly.  coma_conv_wgrad_algo answers the same question for the weight gradient.   */
 int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 int coma_conv_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk,
