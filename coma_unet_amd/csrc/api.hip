@@ -54,11 +54,25 @@ int conv_split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk
                    hipStream_t s, double2* stats, int stats_inst, int* stats_chunks);
 bool conv_split_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed);
+// (algo 5, wide split: algo 4 plus the stride-2 transposed / data-gradient kernel and the stride-2 weight gradients)
+bool conv_split_tconv_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+int conv_split_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                     hipStream_t s, int accum);
+bool conv_split_wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed);
+
+// the split kernel of a problem that resolved to 4: stride 1 under algo 4 and 5, the stride-2 families under algo 5 only
+static int split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                     hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum) {
+  if (conv_split_fwd_ok(d, x, y)) return conv_split_fwd(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
+  return conv_split_tconv(d, x, wk, bias, y, s, accum);      // (statistics not fused: *stats_chunks stays 0, the caller runs the separate pass)
+}
 
 extern "C" int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   if (d->algo == 1) return 1;
   if (conv_point1_ok(d, x, y)) return 1;            // one channel on a side: streaming dot / scale kernels (fp32 weights)
   if (d->algo == 4 && conv_split_fwd_ok(d, x, y)) return 4;   // split: the thick stride-1 3^3 fp32 layers; every other problem as algo 0
+  if (d->algo == 5 && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y))) return 4;   // wide split: + stride-2 transposed / data gradient
   if (conv_mfma_supported(d, x, y)) return 2;       // bf16 tensors: MFMA wherever the shape allows
   if (conv_f32mfma_supported(d, x, y)) return 3;    // fp32 tensors: fp32 MFMA wherever the shape allows
   return 1;
@@ -94,7 +108,7 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
     return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, ws, ws_bytes, wz, accum);
   }
   COMA_CHECK(wk_dtype == COMA_F32, "conv_fwd: fp32 tensors need fp32 kernel-layout weights");
-  if (algo == 4) return conv_split_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr);
+  if (algo == 4) return split_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, accum);
   if (algo == 3) return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, ws, ws_bytes, wz, accum);
   if (conv_point1_ok(d, x, y)) return conv_point1_fwd(d, x, (const float*)wk, bias, y, s);
   return conv_direct_fwd(d, x, (const float*)wk, bias, y, s);
@@ -103,6 +117,7 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
 extern "C" int coma_conv_wgrad_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   if (d->algo == 1 || conv_point1_ok(d, x, dy)) return 1;
   if (d->algo == 4 && conv_split_wgrad_ok(d, x, dy)) return 4;
+  if (d->algo == 5 && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy))) return 4;
   if (!conv_mfma_wgrad_supported(d, x, dy)) return 1;
   return x->dtype == COMA_BF16 ? 2 : 3;
 }
@@ -121,7 +136,7 @@ extern "C" int coma_conv_fwd_norm_stats(const coma_conv_desc* d, const coma_tens
     int fused = 0;
     const int inst = mode == COMA_NORM_INSTANCE ? y->B : 0;      // (the kernels' group count; 0 = one BatchNorm group)
     if (algo_ == 4) {
-      if (int rc = conv_split_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused)) return rc;
+      if (int rc = split_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, 0)) return rc;
     } else if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0)) return rc;
     if (fused) return 0;
   } else {
@@ -156,7 +171,7 @@ extern "C" int coma_conv_wgrad(const coma_conv_desc* d, const coma_tensor* x, co
   }
   if (conv_point1_ok(d, x, dy)) return conv_point1_wgrad(d, x, dy, dwk, s, zeroed);
   const int algo = coma_conv_wgrad_algo(d, x, dy);
-  if (algo == 4) return conv_split_wgrad(d, x, dy, dwk, s, zeroed);
+  if (algo == 4) return conv_split_wgrad_ok(d, x, dy) ? conv_split_wgrad(d, x, dy, dwk, s, zeroed) : conv_split_wgrad2(d, x, dy, dwk, s, zeroed);
   if (algo >= 2) return conv_mfma_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   return conv_direct_wgrad(d, x, dy, dwk, s, zeroed);
 }

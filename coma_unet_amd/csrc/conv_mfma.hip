@@ -2166,16 +2166,7 @@ struct TconvP {
   double2* stats; int stats_inst;
 };
 
-// The 27 (class, tap) pairs in two balanced groups of parity classes -- A = {0, 3, 5, 6} (13 pairs), B = {1, 2, 4, 7} (14
-// pairs) -- each walked by halo offset delta.  A wave holds the accumulators of ONE group at a time (4 classes x 2 M-tiles =
-// 128 registers; all 8 classes at once spilled 135 registers next to the 22 staging pieces in flight), so a tile is two
-// passes over its channel chunks, each staging the halo and only the 13 / 14 taps it needs (75 KB of LDS).  Every tap
-// belongs to exactly one pair: LDS weight slot k of a pass holds the tap of pair k.
-__device__ constexpr int TC_NP[2] = {13, 14};
-__device__ constexpr int TC_DELTA[2][14] = {{0, 0, 0, 0, 1, 1, 2, 2, 3, 4, 4, 5, 6, 6}, {0, 0, 0, 0, 1, 1, 2, 2, 3, 4, 4, 5, 6, 7}};
-__device__ constexpr int TC_LCLS[2][14] = {{0, 1, 2, 3, 1, 2, 1, 3, 1, 2, 3, 2, 3, 3}, {0, 1, 2, 3, 0, 3, 1, 3, 3, 2, 3, 3, 3, 3}};
-__device__ constexpr int TC_TAP[2][14] = {{13, 17, 23, 25, 15, 21, 11, 19, 9, 5, 7, 3, 1, 27}, {14, 16, 22, 26, 12, 24, 10, 20, 18, 4, 8, 6, 2, 0}};
-__device__ constexpr int TC_CLS[2][4] = {{0, 3, 5, 6}, {1, 2, 4, 7}};
+// (TC_NP / TC_DELTA / TC_LCLS / TC_TAP / TC_CLS, the 27 (class, tap) pairs in two passes: conv_tiles.h)
 
 // STATS: the fused norm statistics (forward of the up-convolutions); without them the kernel also takes COMA_ACCUMULATE
 // (data gradients).  Two instantiations because the statistics' 32 accumulators are live across the whole tile loop: the
@@ -4638,4 +4629,13 @@ int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_te
 // the fp32 problems conv_mfma_halo<float> runs on conv_mfma_halo2_k<2, 16, 1, 1, float>: what conv_split.hip takes under algo 4
 bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   return conv_f32mfma_supported(d, x, y) && !thin16f_ok(d, x, y) && f32_halo_ok(d, x, y) && x->W >= 32;
+}
+
+// the fp32 problems conv_mfma_fwd runs on conv_mfma_tconv_k<float, *> / conv_mfma_wgrad on conv_f32_wgrad16_k<2, *>: what
+// conv_split.hip adds under algo 5
+bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return x->dtype == COMA_F32 && conv_f32mfma_supported(d, x, y) && !thin16f_ok(d, x, y) && !f32_halo_ok(d, x, y) && tconv_ok(d, x, y);
+}
+bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  return d->stride == 2 && x->dtype == COMA_F32 && conv_mfma_wgrad_supported(d, x, dy) && !thin16f_wgrad_ok(d, x, dy) && f32_wgrad16_ok(d, x, dy);
 }

@@ -536,3 +536,490 @@ int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_t
   COMA_LAUNCH_CHECK();
   return 0;
 }
+
+// =====================================================================================
+// Wide split (coma_conv_desc.algo = 5): the stride-2 families.
+//   conv_split_tconv_k  -- stride-2 3x3x3 transposed convolution / data gradient of the stride-2 convolutions
+//                          (the problems of conv_mfma_tconv_k<float, *>)
+//   conv_split_wgrad2_k -- stride-2 and transposed 3x3x3 weight gradient (the problems of conv_f32_wgrad16_k<2, *>)
+// =====================================================================================
+bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));      // (native vectors for the staging registers: see conv_mfma_duo_k)
+
+__device__ __forceinline__ void split4(const u32x4_t& v, uint2& hi, uint2& lo) { split4(make_uint4(v[0], v[1], v[2], v[3]), hi, lo); }
+
+// =====================================================================================
+// conv_split_tconv_k -- the structure of conv_mfma_tconv_k<float, STATS> (see there for the parity classes and the two
+// passes): a coarse 2 x 4 x 32 tile plus a one-voxel high-side halo (495 rows), the 27 (class, tap) pairs walked by halo
+// offset, persistent blocks, the next step's 15 fp32 staging pieces fetched inside the MFMA loop.  An LDS row holds the same
+// 64 bytes (16 channels), now [16 bf16 hi][16 bf16 lo]: the two 16-byte fragment reads per row that fed four
+// v_mfma_f32_32x32x2_f32 feed three v_mfma_f32_32x32x16_bf16, and the 75 KB image keeps its size.
+// COMA_ACCUMULATE is kept (the stride-2 data gradients add into the skip connection's gradient).  The norm statistics are
+// NOT fused: their 32 accumulators, live across the tile loop next to 128 accumulator and 60 staging registers plus the
+// conversion temporaries, spilled 24 registers to scratch; the caller runs the separate statistics pass instead.
+// =====================================================================================
+struct SplitTconvP {
+  const float* x; int ldx; long sbx; int D, H, W, C;     // coarse input
+  float* y; int ldy; long sby; int Do, Ho, Wo, N;        // fine output (2 x coarse, or one less, per dimension)
+  const float* w; long wsb;                              // [b][27][N][C]
+  const float* bias; int bsb;
+  int ntx, nty, ntz, ids_total, ids_per_block;
+  unsigned xbytes, wbytes;
+  int accum;
+};
+
+__global__ __launch_bounds__(256, 1) void conv_split_tconv_k(SplitTconvP p) {
+  constexpr int CK = 16;
+  constexpr int TX = 32, TY = 4, TZ = 2, HX = TX + 1, HY = TY + 1, HZ = TZ + 1, HV = HX * HY * HZ;   // 495 halo rows
+  constexpr int P = 80;
+  constexpr int HP = HV * 4, HIT = (HP + 255) / 256;   // 1980 halo pieces of 4 fp32 -> 8 per thread
+  constexpr int WS = 14, WP = WS * 32 * 4, WIT = WP / 256;   // 14 weight slots = 1792 pieces -> 7 per thread
+  static_assert(WP % 256 == 0 && HIT + WIT <= 2 * 13, "at most two prefetch pieces per (class, tap) pair");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Wl = smem;                                     // [14 * 32][80]
+  char* Hl = smem + WS * 32 * P;                       // [HV][80]
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int b = blockIdx.z, n0 = blockIdx.y * 32;
+  const int fr = lane & 31, fh = lane >> 5;
+  const float* xb = p.x + (long)b * p.sbx;
+  const float* wb = p.w + (long)b * p.wsb;
+  float* yb = p.y + (long)b * p.sby;
+  const int nchunks = p.C / CK;
+  constexpr unsigned OOB = 0x7fff0000u;
+
+  // ---- staging descriptors (tile independent), as conv_mfma_tconv_k: byte offset of a halo piece relative to the tile
+  // origin, its halo coordinates as three 9-bit fields tested against the packed per-tile limits with one subtraction ----
+  unsigned h_boff[HIT], h_zyx[HIT];
+#pragma unroll
+  for (int it = 0; it < HIT; ++it) {
+    const int piece = tid + 256 * it;
+    const int row = piece >> 2, ch = piece & 3;
+    const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+    h_boff[it] = (unsigned)((((hz * p.H + hy) * p.W + hx) * p.ldx + ch * 4) * 4);
+    h_zyx[it] = piece < HP ? ((unsigned)hz << 20) | ((unsigned)hy << 10) | (unsigned)hx : 0x1ff00000u;
+  }
+  const int h_lds0 = (tid >> 2) * P + (tid & 3) * 8;       // hi half of piece `it`: + it * 64 rows; lo at + 32
+  constexpr unsigned GUARD = (1u << 29) | (1u << 19) | (1u << 9);
+  const int w_s0 = tid >> 7, w_n = (tid >> 2) & 31, w_ch = tid & 3;
+  const int w_lds0 = (w_s0 * 32 + w_n) * P + w_ch * 8;
+  constexpr int W_LSTEP = 2 * 32 * P;
+  unsigned w_row = (unsigned)(((long)(n0 + w_n) * p.C + w_ch * 4) * 4L);
+  const unsigned w_tap = (unsigned)((long)p.N * p.C * 4L);                      // bytes between two taps
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.xbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, p.wbytes, 0x00020000);
+
+  int a_base[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int j = wid * 2 + i;
+    a_base[i] = (((j >> 2) * HY + (j & 3)) * HX + fr) * P + fh * 16;
+  }
+  const int w_base = fr * P + fh * 16;
+
+  u32x4_t hreg[HIT], wreg[WIT];
+  auto tile_lim = [&](int z0, int y0, int x0) -> unsigned {
+    const int lz = p.D - z0 - 1 < 511 ? p.D - z0 - 1 : 511, ly = p.H - y0 - 1 < 511 ? p.H - y0 - 1 : 511, lx = p.W - x0 - 1 < 511 ? p.W - x0 - 1 : 511;
+    return ((unsigned)lz << 20) | ((unsigned)ly << 10) | (unsigned)lx | GUARD;
+  };
+  auto halo_piece = [&](const __amdgpu_buffer_rsrc_t& rs, int it, unsigned lim, unsigned org_b) -> u32x4_t {
+    const bool ok = ((lim - h_zyx[it]) & GUARD) == GUARD;
+    const unsigned voff = ok ? org_b + h_boff[it] : OOB;
+    return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
+  };
+  auto w_piece = [&](const __amdgpu_buffer_rsrc_t& rs, int it, int grp, int c0_b) -> u32x4_t {
+    const int t0 = grp ? TC_TAP[1][2 * it] : TC_TAP[0][2 * it], t1 = grp ? TC_TAP[1][2 * it + 1] : TC_TAP[0][2 * it + 1];
+    const int tap = w_s0 ? t1 : t0;
+    asm volatile("" : "+v"(w_row));                  // (not hoisted back into loop-invariant registers)
+    const unsigned voff = tap < 27 ? w_row + (unsigned)tap * w_tap : OOB;
+    return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c0_b, 0);
+  };
+  auto tile_org = [&](int z0, int y0, int x0, int c0) -> unsigned {
+    return (unsigned)((((long)(z0 * p.H + y0) * p.W + x0) * p.ldx + c0) * 4L);
+  };
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  if (id >= id_end) return;
+  {
+    const unsigned org = tile_org(tiz * TZ, tiy * TY, tix * TX, 0), lim = tile_lim(tiz * TZ, tiy * TY, tix * TX);
+#pragma unroll
+    for (int it = 0; it < HIT; ++it) hreg[it] = halo_piece(rs_x, it, lim, org);
+#pragma unroll
+    for (int it = 0; it < WIT; ++it) wreg[it] = w_piece(rs_w, it, 0, 0);
+  }
+
+  const bool accum = p.accum != 0;
+
+  while (id < id_end) {
+    const int x0 = tix * TX, y0 = tiy * TY, z0 = tiz * TZ;
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+
+#pragma unroll
+    for (int grp = 0; grp < 2; ++grp) {
+      f32x16_t acc[4][2];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[c][i][e] = 0.f;
+
+      for (int cc = 0; cc < nchunks; ++cc) {
+        __syncthreads();                       // all waves finished reading the previous halo / weights
+        // the split happens here: one conversion per staged element, two 8-byte LDS stores per piece
+#pragma unroll
+        for (int it = 0; it < HIT; ++it)
+          if (tid + 256 * it < HP) {
+            uint2 hi, lo;
+            split4(hreg[it], hi, lo);
+            *reinterpret_cast<uint2*>(Hl + h_lds0 + it * 64 * P) = hi;
+            *reinterpret_cast<uint2*>(Hl + h_lds0 + it * 64 * P + 32) = lo;
+          }
+#pragma unroll
+        for (int it = 0; it < WIT; ++it) {
+          uint2 hi, lo;
+          split4(wreg[it], hi, lo);
+          *reinterpret_cast<uint2*>(Wl + w_lds0 + it * W_LSTEP) = hi;
+          *reinterpret_cast<uint2*>(Wl + w_lds0 + it * W_LSTEP + 32) = lo;
+        }
+        __syncthreads();
+        // what to prefetch while this step computes: the next chunk of this pass, chunk 0 of the tile's second pass, or
+        // chunk 0 / pass A of the next tile; through descriptors whose range is zero when there is nothing left (no branch)
+        const bool same_pass = cc + 1 < nchunks;
+        const bool same_tile = same_pass || grp == 0;
+        const bool pref = same_tile || has_next;
+        const int pz = same_tile ? z0 : ntiz * TZ, py = same_tile ? y0 : ntiy * TY, px = same_tile ? x0 : ntix * TX;
+        const int pc0 = same_pass ? (cc + 1) * CK : 0;
+        const int pgrp = same_pass ? grp : 1 - grp;
+        const __amdgpu_buffer_rsrc_t rs_xp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, pref ? p.xbytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_wp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, pref ? p.wbytes : 0, 0x00020000);
+        const unsigned porg = tile_org(pz, py, px, pc0), plim = tile_lim(pz, py, px);
+        const int pc0_b = pc0 * 4;
+
+        uint4 wv[2][2], xv[2][2][2];           // fragments one pair (weights) / one delta (voxels) ahead: [.][0] = hi, [.][1] = lo
+        auto rd_w = [&](int k, int bf) {
+#pragma unroll
+          for (int hl = 0; hl < 2; ++hl) wv[bf][hl] = *reinterpret_cast<const uint4*>(Wl + w_base + k * 32 * P + hl * 32);
+        };
+        auto rd_x = [&](int di, int bf) {
+          const int doff = ((((di >> 2) & 1) * HY + ((di >> 1) & 1)) * HX + (di & 1)) * P;
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int hl = 0; hl < 2; ++hl) xv[bf][i][hl] = *reinterpret_cast<const uint4*>(Hl + a_base[i] + doff + hl * 32);
+        };
+        rd_x(0, 0);
+        rd_w(0, 0);
+        constexpr int NPMAX = 14;
+#pragma unroll
+        for (int k = 0; k < NPMAX; ++k) {
+          if (k >= TC_NP[grp]) continue;         // (compile time: grp and k are unrolled)
+          const int di = TC_DELTA[grp][k], lc = TC_LCLS[grp][k];
+          if (k + 1 < TC_NP[grp]) {
+            rd_w(k + 1, (k + 1) & 1);
+            if (TC_DELTA[grp][k + 1] != di) rd_x(TC_DELTA[grp][k + 1], TC_DELTA[grp][k + 1] & 1);
+          }
+          // prefetch pieces: 15 per step over 13 / 14 pairs (one per pair, the last ones two)
+          if (k < WIT) wreg[k] = w_piece(rs_wp, k, pgrp, pc0_b);
+          else if (k - WIT < HIT) hreg[k - WIT] = halo_piece(rs_xp, k - WIT, plim, porg);
+          if (k == TC_NP[grp] - 1) {
+#pragma unroll
+            for (int r = TC_NP[grp] - WIT; r < HIT; ++r) hreg[r] = halo_piece(rs_xp, r, plim, porg);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) acc[lc][i] = mma3(wv[k & 1][0], wv[k & 1][1], xv[di & 1][i][0], xv[di & 1][i][1], acc[lc][i]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // ---- epilogue of this pass's 4 classes: lane = one coarse voxel of each M-tile, 4 groups of 4 consecutive channels ----
+      const bool has_bias = p.bias != nullptr;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int j = wid * 2 + i;
+        const int cz = z0 + (j >> 2), cy = y0 + (j & 3), cx = x0 + fr;
+        const bool cin = cz < p.D && cy < p.H && cx < p.W;
+        const bool vz1 = 2 * cz + 1 < p.Do, vy1 = 2 * cy + 1 < p.Ho, vx1 = 2 * cx + 1 < p.Wo;      // (odd fine sizes: the last odd plane is absent)
+        const long vbase = ((long)(2 * cz * p.Ho + 2 * cy) * p.Wo + 2 * cx) * p.ldy + n0;         // fine voxel (2cz, 2cy, 2cx)
+#pragma unroll
+        for (int lc = 0; lc < 4; ++lc) {
+          __builtin_amdgcn_sched_barrier(0);     // one class at a time: interleaved, the 8 unrolled instances spill
+          const int cls = TC_CLS[grp][lc];
+          const bool valid = cin && (!(cls & 4) || vz1) && (!(cls & 2) || vy1) && (!(cls & 1) || vx1);
+          const long voff = vbase + ((long)(((cls >> 2) & 1) * p.Ho + ((cls >> 1) & 1)) * p.Wo + (cls & 1)) * p.ldy;
+          float* dst = yb + voff + 4 * fh;
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            float of[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) of[q] = acc[lc][i][g4 * 4 + q];
+            if (has_bias) {                        // (uniform)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) of[q] += p.bias[b * p.bsb + n0 + 8 * g4 + 4 * fh + q];
+            }
+            float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (accum && valid) old = *reinterpret_cast<const float4*>(dst + 8 * g4);
+            const float o[4] = {of[0] + old.x, of[1] + old.y, of[2] + old.z, of[3] + old.w};
+            if (valid) *reinterpret_cast<float4*>(dst + 8 * g4) = make_float4(o[0], o[1], o[2], o[3]);
+          }
+        }
+      }
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+}
+
+bool conv_split_tconv_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return conv_f32_tconv_problem(d, x, y);
+}
+
+int conv_split_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                     hipStream_t s, int accum) {
+  COMA_CHECK(conv_split_tconv_ok(d, x, y), "conv_split_tconv: problem not in the split kernel's scope");
+  COMA_CHECK(aligned16(x->data) && aligned16(y->data) && aligned16(wk), "conv_split_tconv: operands must be 16-byte aligned");
+  SplitTconvP q;
+  q.x = (const float*)x->data; q.ldx = (int)x->ld; q.sbx = x->sb; q.D = x->D; q.H = x->H; q.W = x->W; q.C = x->C;
+  q.y = (float*)y->data; q.ldy = (int)y->ld; q.sby = y->sb; q.Do = y->D; q.Ho = y->H; q.Wo = y->W; q.N = y->C;
+  q.w = (const float*)wk; q.wsb = d->per_sample_w ? 27L * y->C * x->C : 0;
+  q.bias = bias; q.bsb = d->per_sample_w ? y->C : 0;
+  const unsigned long long wb_ = 27ull * y->C * x->C * 4;
+  COMA_CHECK(wb_ < 0x7fff0000ull, "conv_split_tconv: weight set too large for 32-bit buffer offsets");
+  q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
+  q.wbytes = (unsigned)wb_;
+  q.accum = accum;
+  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
+  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
+  const int nblk_n = y->C / 32;
+  int gx = 512 / (nblk_n * x->B);                      // one block per CU, about two rounds
+  if (gx < 1) gx = 1;
+  if (gx > q.ids_total) gx = q.ids_total;
+  q.ids_per_block = (q.ids_total + gx - 1) / gx;
+  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_tconv_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+  const size_t lds = (size_t)(33 * 5 * 3 + 14 * 32) * 80;
+  coma_set_kernel_tag("conv_split_tconv_k");
+  const dim3 grid((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B);
+  hipLaunchKernelGGL(conv_split_tconv_k, grid, dim3(256), lds, s, q);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================
+// conv_split_wgrad2_k -- the frame of conv_f32_wgrad16_k<2, FORM> (a block owns a 32 x 32 (n, c) weight tile and a run of
+// 1 x 2 x 32-voxel DENSE tiles on the coarse grid with their 3 x 5 x 65 = 975-row GATHERED region on the fine grid) with
+// the MFMA body of conv_split_wgrad_k: four bf16 images (dense hi / lo, gathered hi / lo: 133 KB, the bytes of the fp32
+// images), voxels along K, operands read transposed with ds_read_b64_tr_b16, the 27 taps dealt to the 4 waves, fp32
+// accumulators kept over the block's tiles, fp32 atomic merge.  The stride lives in the lanes' row addresses: dense voxel
+// m of a row pairs with gathered row 2 m + tap.
+// FORM 0: stride-2 convolution (dense dy -> MFMA rows n, gathered x -> columns c);
+// FORM 1: transposed stride-2 convolution (dense x -> columns c, gathered dy -> rows n).
+// =====================================================================================
+struct SplitWgrad2P {
+  const float* dn; int ldd; long sbd; int Mz, My, Mx;      // dense operand on the coarse grid
+  const float* ga; int ldg; long sbg; int Gz, Gy, Gx;      // gathered operand on the fine grid
+  int N, C;
+  unsigned dbytes, gbytes;
+  int ntx, nty, ntz, ids_total, ids_per_block, cblocks;
+  float* dwk; long wsb;
+};
+
+template <int FORM>
+__global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
+  constexpr int TX = 32, TY = 2, TZ = 1, TM = TX * TY * TZ;
+  constexpr int HX = 2 * TX + 1, HY = 2 * TY + 1, HZ = 2 * TZ + 1, HV = HX * HY * HZ;      // 65 x 5 x 3
+  constexpr int PR = 64;                                // LDS row pitch (bytes): 32 bf16 channels
+  constexpr int HIT = (HV * 8 + 255) / 256, DIT = TM * 8 / 256, NIT = HIT + DIT;      // 16-byte fp32 pieces per thread: 31 + 2
+  constexpr int MAXT = 7;                               // taps per wave
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Gh = smem;                                      // [HV][64] gathered hi
+  char* Gl = Gh + HV * PR;                              //          gathered lo
+  char* Dh = Gl + HV * PR;                              // [TM][64] dense hi
+  char* Dl = Dh + TM * PR;                              //          dense lo
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z;
+  const int n0 = (blockIdx.y / p.cblocks) * 32, c0 = (blockIdx.y % p.cblocks) * 32;
+  const int dch0 = FORM == 0 ? n0 : c0, gch0 = FORM == 0 ? c0 : n0;      // channel block of the dense / gathered operand
+  const int dchn = FORM == 0 ? p.N : p.C, gchn = FORM == 0 ? p.C : p.N;
+  const float* dnb = p.dn + (long)b * p.sbd + dch0;
+  const float* gab = p.ga + (long)b * p.sbg + gch0;
+  const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, p.gbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, p.dbytes, 0x00020000);
+  constexpr unsigned OOB = 0x7fff0000u;
+
+  // staging: piece = tid + 256 it -> (row = piece >> 3, 4-channel piece = tid & 7); gathered positions relative to
+  // 2 * tile origin - 1, dense positions relative to the tile origin - 1.  A piece outside its volume or past the tensor's
+  // channels reads as zero.
+  const int chq = (tid & 7) * 4;
+  const unsigned choff = (unsigned)(chq * 4);
+  const bool ch_g = gch0 + chq < gchn, ch_d = dch0 + chq < dchn;
+  int s_pos[NIT];                                       // packed z | y << 4 | x << 8
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (it < HIT) {
+      const int row = (tid + 256 * it) >> 3;
+      const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+      s_pos[it] = row < HV ? (hz | (hy << 4) | (hx << 8)) : (15 | (15 << 4) | (1023 << 8));
+    } else {
+      const int row = (tid + 256 * (it - HIT)) >> 3;
+      s_pos[it] = ((row / (TY * 32)) + 1) | ((((row >> 5) % TY) + 1) << 4) | (((row & 31) + 1) << 8);
+    }
+  }
+  uint4 sreg[NIT];
+  auto issue_all = [&](int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rg, const __amdgpu_buffer_rsrc_t& rd) __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int sc = it < HIT ? 2 : 1;
+      const int gz = sc * z0 - 1 + (s_pos[it] & 15), gy = sc * y0 - 1 + ((s_pos[it] >> 4) & 15), gx = sc * x0 - 1 + (s_pos[it] >> 8);
+      const bool ok = it < HIT ? ((unsigned)gz < (unsigned)p.Gz && (unsigned)gy < (unsigned)p.Gy && (unsigned)gx < (unsigned)p.Gx && ch_g)
+                               : ((unsigned)gz < (unsigned)p.Mz && (unsigned)gy < (unsigned)p.My && (unsigned)gx < (unsigned)p.Mx && ch_d);
+      const unsigned off = it < HIT ? (unsigned)(((gz * p.Gy + gy) * p.Gx + gx) * p.ldg) * 4u + choff
+                                    : (unsigned)(((gz * p.My + gy) * p.Mx + gx) * p.ldd) * 4u + choff;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(it < HIT ? rg : rd, ok ? off : OOB, 0, 0);
+      sreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
+  auto store_tile = [&]() __attribute__((always_inline)) {      // the split: one conversion per staged element
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      uint2 hi, lo;
+      split4(sreg[it], hi, lo);
+      if (it < HIT) {
+        const int piece = tid + 256 * it;
+        if ((piece >> 3) < HV) { *reinterpret_cast<uint2*>(Gh + piece * 8) = hi; *reinterpret_cast<uint2*>(Gl + piece * 8) = lo; }
+      } else {
+        const int piece = tid + 256 * (it - HIT);
+        *reinterpret_cast<uint2*>(Dh + piece * 8) = hi; *reinterpret_cast<uint2*>(Dl + piece * 8) = lo;
+      }
+    }
+  };
+
+  f32x16_t acc[MAXT];
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+  // per-wave tap list (wave-uniform): tap = wid + 4 t; byte offset of the tap's shift in the gathered image
+  int toff_w[MAXT];
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) {
+    const int tap = wid + 4 * t;
+    const int kx = tap % 3, ky = (tap / 3) % 3, kz = tap / 9;
+    toff_w[t] = __builtin_amdgcn_readfirstlane(((kz * HY + ky) * HX + kx) * PR);
+  }
+  const bool last_tap = wid + 4 * (MAXT - 1) < 27;      // (wave 3 has six taps)
+  // lane roles of the transposed reads (as conv_split_wgrad_k): a 16-lane group covers 4 voxels x 16 channels per read
+  const int g16 = lane >> 4, li = lane & 15, q4 = li >> 2, pp = li & 3;
+  const int chan_b = ((g16 & 1) * 16 + 4 * pp) * 2;     // byte offset of this lane's 4 channels in the 32-channel row
+  const int vrow = 8 * (g16 >> 1) + q4;                 // voxel (within a 16-voxel K step) whose row this lane addresses
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  if (id >= id_end) return;
+  issue_all(tiz * TZ, tiy * TY, tix * TX, rs_g, rs_d);
+  while (id < id_end) {
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+    const __amdgpu_buffer_rsrc_t rn_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, has_next ? p.gbytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, has_next ? p.dbytes : 0, 0x00020000);
+    __syncthreads();
+    store_tile();
+    __syncthreads();
+    issue_all(ntiz * TZ, ntiy * TY, ntix * TX, rn_g, rn_d);
+    // 4 K steps of 16 dense voxels: step ks = half an x row of the tile
+#pragma unroll
+    for (int ks = 0; ks < TM / 16; ++ks) {
+      const int r = ks >> 1, xh = (ks & 1) * 16 + vrow;                      // dense row y of the tile, x within it
+      const int d1 = (r * 32 + xh) * PR + chan_b;
+      const int g1 = ((2 * r) * HX + 2 * xh) * PR + chan_b;                  // the same voxel's tap (0, 0, 0) in the gathered image
+      auto frag = [&](const char* base, int step) __attribute__((always_inline)) -> uint4 {
+        const s4_t u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base));
+        const s4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base + step));
+        const bf16x8_t f = (bf16x8_t){u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+        return *reinterpret_cast<const uint4*>(&f);
+      };
+      const uint4 dh = frag(Dh + d1, 4 * PR), dl = frag(Dl + d1, 4 * PR);
+#pragma unroll
+      for (int t = 0; t < MAXT; ++t) {
+        if (t < MAXT - 1 || last_tap) {
+          const uint4 gh = frag(Gh + g1 + toff_w[t], 8 * PR), gl = frag(Gl + g1 + toff_w[t], 8 * PR);
+          acc[t] = FORM == 0 ? mma3(dh, dl, gh, gl, acc[t]) : mma3(gh, gl, dh, dl, acc[t]);
+        }
+      }
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+  // ---- merge into dwk[b][tap][n][c]: MFMA rows = n, columns = c ----
+  float* wout = p.dwk + (long)b * p.wsb;
+  const int fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < MAXT; ++t) {
+    const int tap = wid + 4 * t;
+    if (tap < 27) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int n = n0 + (e & 3) + 8 * (e >> 2) + 4 * fh, c = c0 + fr;
+        if (n < p.N && c < p.C) atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, acc[t][e]);
+      }
+    }
+  }
+}
+
+bool conv_split_wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  const coma_tensor* dn = d->form == 0 ? dy : x;
+  const coma_tensor* ga = d->form == 0 ? x : dy;
+  // (the dense grid is the coarse one: every gathered row 2 m - 1 + tap of a dense voxel m is tested against the fine grid)
+  return conv_f32_wgrad16s2_problem(d, x, dy) && d->pad == 1 && dn->B == ga->B &&
+         ga->D <= 2 * dn->D && ga->H <= 2 * dn->H && ga->W <= 2 * dn->W;
+}
+
+int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
+  COMA_CHECK(conv_split_wgrad2_ok(d, x, dy), "conv_split_wgrad2: problem not in the split kernel's scope");
+  const coma_tensor* dn = d->form == 0 ? dy : x;
+  const coma_tensor* ga = d->form == 0 ? x : dy;
+  SplitWgrad2P q;
+  q.dn = (const float*)dn->data; q.ldd = (int)dn->ld; q.sbd = dn->sb; q.Mz = dn->D; q.My = dn->H; q.Mx = dn->W;
+  q.ga = (const float*)ga->data; q.ldg = (int)ga->ld; q.sbg = ga->sb; q.Gz = ga->D; q.Gy = ga->H; q.Gx = ga->W;
+  q.N = dy->C; q.C = x->C;
+  // (descriptor ranges are measured from the block's channel offset; the voxel and channel tests keep every piece inside)
+  q.dbytes = (unsigned)((unsigned long long)t_vox(dn) * dn->ld * 4);
+  q.gbytes = (unsigned)((unsigned long long)t_vox(ga) * ga->ld * 4);
+  q.ntx = (q.Mx + 31) / 32; q.nty = (q.My + 1) / 2; q.ntz = q.Mz;
+  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
+  q.cblocks = (q.C + 31) / 32;
+  const int pairs = q.cblocks * ((q.N + 31) / 32);
+  int gx = 256 / (pairs * x->B);                       // one block per CU, one round: a second round repeats the atomic merge
+  if (gx < 1) gx = 1;
+  if (gx > q.ids_total) gx = q.ids_total;
+  q.ids_per_block = (q.ids_total + gx - 1) / gx;
+  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
+  q.wsb = d->per_sample_w ? wsz1 : 0;
+  q.dwk = dwk;
+  if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const size_t lds = (size_t)2 * (65 * 5 * 3 + 64) * 64;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)conv_split_wgrad2_k<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv_split_wgrad2_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  const dim3 grid((unsigned)gx, (unsigned)pairs, (unsigned)x->B);
+  coma_set_kernel_tag("conv_split_wgrad2_k<%d>", d->form);
+  if (d->form == 0) hipLaunchKernelGGL(conv_split_wgrad2_k<0>, grid, dim3(256), lds, s, q);
+  else hipLaunchKernelGGL(conv_split_wgrad2_k<1>, grid, dim3(256), lds, s, q);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}

@@ -37,3 +37,15 @@ __device__ __forceinline__ bool tile_coords(int id, int ntx, int nty, int ntz, i
   tiz = tzb * 8 + zin;
   return tiz < ntz && tix < ntx;
 }
+
+// ---- stride-2 transposed convolution (conv_mfma_tconv_k, conv_split_tconv_k) ----
+// The 27 (class, tap) pairs in two balanced groups of parity classes -- A = {0, 3, 5, 6} (13 pairs), B = {1, 2, 4, 7} (14
+// pairs) -- each walked by halo offset delta.  A wave holds the accumulators of ONE group at a time (4 classes x 2 M-tiles =
+// 128 registers; all 8 classes at once spilled 135 registers next to the 22 staging pieces in flight), so a tile is two
+// passes over its channel chunks, each staging the halo and only the 13 / 14 taps it needs (75 KB of LDS).  Every tap
+// belongs to exactly one pair: LDS weight slot k of a pass holds the tap of pair k.
+__device__ constexpr int TC_NP[2] = {13, 14};
+__device__ constexpr int TC_DELTA[2][14] = {{0, 0, 0, 0, 1, 1, 2, 2, 3, 4, 4, 5, 6, 6}, {0, 0, 0, 0, 1, 1, 2, 2, 3, 4, 4, 5, 6, 7}};
+__device__ constexpr int TC_LCLS[2][14] = {{0, 1, 2, 3, 1, 2, 1, 3, 1, 2, 3, 2, 3, 3}, {0, 1, 2, 3, 0, 3, 1, 3, 3, 2, 3, 3, 3, 3}};
+__device__ constexpr int TC_TAP[2][14] = {{13, 17, 23, 25, 15, 21, 11, 19, 9, 5, 7, 3, 1, 27}, {14, 16, 22, 26, 12, 24, 10, 20, 18, 4, 8, 6, 2, 0}};
+__device__ constexpr int TC_CLS[2][4] = {{0, 3, 5, 6}, {1, 2, 4, 7}};

@@ -95,7 +95,15 @@ typedef struct coma_conv_desc {
                              W >= 32 (forward, data gradient, weight gradient) form every product from a two-term bf16
                              split of both operands on v_mfma_f32_32x32x16_bf16 (three MFMAs, fp32 accumulation: error
                              below 2^-14 |a||b| per product); coma_conv_pick_algo / coma_conv_wgrad_algo answer 4 there.
-                             Every other problem, and bf16 tensors, resolve exactly as algo 0 does. */
+                             Every other problem, and bf16 tensors, resolve exactly as algo 0 does.
+                             5 wide split: everything algo 4 resolves to the split kernels, plus the stride-2 3x3x3
+                             families with a coarse W >= 32 on fp32 tensors: the transposed convolution (form 1, stride 2:
+                             forward of the up-convolutions and data gradient of the stride-2 convolutions, per-sample or
+                             shared weights, COMA_ACCUMULATE and the fused statistics kept) and the stride-2 / transposed
+                             weight gradients.  coma_conv_pick_algo / coma_conv_wgrad_algo answer 4 there too (the host's
+                             weight preparation is the same: fp32 kernel-layout weights); coma_conv_accumulate_ok and
+                             coma_conv_fwd_ws_bytes answer what they answer under algo 0.  Every other problem, and bf16
+                             tensors, resolve exactly as algo 0 does. */
 } coma_conv_desc;
 
 int         coma_abi_version(void);
@@ -138,7 +146,7 @@ int coma_routing_bwd(const float* cov, int32_t B, int32_t NC, const float* r, in
 
 /* ---- convolution (nn.Conv3d / nn.ConvTranspose3d and their data-gradients) ---- */
 /* which kernel family d->algo resolves to for this problem: 1 direct (wants fp32 wk), 2 bf16 MFMA
- * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk), 4 split-bf16 MFMA (algo 4 only; fp32
+ * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk), 4 split-bf16 MFMA (algo 4 and 5 only; fp32
  * tensors, wants fp32 wk: the split is done inside the library).  The host prepares the kernel-layout
  * weights accordingly.  coma_conv_wgrad_algo answers the same question for the weight gradient.   */
 int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
