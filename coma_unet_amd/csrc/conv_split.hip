@@ -12,16 +12,28 @@
 //
 //   conv_split_halo_k  -- stride-1 3x3x3 forward / data gradient (the problems of conv_mfma_halo2_k<2, 16, 1, 1, float>)
 //   conv_split_wgrad_k -- stride-1 3x3x3 weight gradient          (the problems of conv_f32_wgrad16_k<1, 0>)
+// and, under algo = 5 (wide split), the stride-2 families:
+//   conv_split_tconv_k  -- stride-2 3x3x3 transposed convolution / data gradient of the stride-2 convolutions
+//                          (the problems of conv_mfma_tconv_k<float, *>)
+//   conv_split_wgrad2_k -- stride-2 and transposed 3x3x3 weight gradient (the problems of conv_f32_wgrad16_k<2, *>)
 #include "common.h"
 #include "conv_tiles.h"
 
 typedef __attribute__((ext_vector_type(4))) short s4_t;
 typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 
-// conv_mfma.hip: the fp32 problems its halo-tiled kernel takes at W >= 32
+// conv_mfma.hip: the fp32 problems its kernels take (halo-tiled at W >= 32; transposed stride-2; stride-2 weight gradients)
 bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// every kernel here asks for more dynamic LDS than the 64 KB default: raise the kernel's limit to the CU's 160 KB, once
+template <auto KERNEL> static void set_max_lds() {
+  static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)once;
+}
 
 // 4 fp32 (one 16-byte staging piece) -> 4 bf16 hi + 4 bf16 lo
 __device__ __forceinline__ void split4(const uint4& v, uint2& hi, uint2& lo) {
@@ -321,230 +333,18 @@ int conv_split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk
     q.wbytes = (unsigned)wb_;
   }
   q.st16 = y->ld % 4 == 0 && y->sb % 4 == 0 && aligned16(y->data);
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   const int nblk_n = (q.N + 31) / 32;
-  int gx = 256 / (nblk_n * x->B);                      // one block per CU, one round
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 256, nblk_n * x->B);      // one block per CU, one round
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   q.stats = nullptr; q.stats_inst = stats_inst;
   if (stats) { q.stats = stats; *stats_chunks = 1; }
   const size_t lds = (size_t)(34 * 6 * 4 + 27 * 32) * 80;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_halo_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+  set_max_lds<conv_split_halo_k>();
   coma_set_kernel_tag("conv_split_halo_k");
-  hipLaunchKernelGGL(conv_split_halo_k, dim3((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B), dim3(256), lds, s, q);
+  hipLaunchKernelGGL(conv_split_halo_k, dim3((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B), dim3(256), lds, s, q);
   COMA_LAUNCH_CHECK();
   return 0;
 }
-
-// =====================================================================================
-// conv_split_wgrad_k -- dwk[b][tap][n][c] += sum_m dy[m][n] * x[m + tap - 1][c], the reduction index is the voxel.
-// The frame of conv_f32_wgrad16_k<1, 0> (a block owns a 32 x 32 (n, c) weight tile and a run of 2 x 4 x 32-voxel tiles;
-// the dy tile and the 4 x 6 x 34 x halo are staged by buffer loads, the next tile's 34 pieces per thread in flight while
-// this one computes) with the MFMA body of conv_mfma_wgrad_k<1, 1, 0>: both operands are [voxel][32 channels] bf16 images
-// (64-byte rows) read transposed with ds_read_b64_tr_b16, the 27 taps are dealt to the 4 waves (7, 7, 7, 6) whose 32 x 32
-// fp32 accumulators stay in registers over the block's tiles and merge into dwk with fp32 atomics at the end.
-// Each image exists twice (hi, lo): together the bytes of the fp32 images of conv_f32_wgrad16_k (134 KB).
-// =====================================================================================
-struct SplitWgradP {
-  const float* dy; int ldd; long sbd;       // dense operand, N channels
-  const float* x; int ldg; long sbg;        // gathered operand, C channels (same grid: stride 1, pad 1)
-  int D, H, W, N, C;
-  unsigned dbytes, gbytes;
-  int ntx, nty, ntz, ids_total, ids_per_block, cblocks;
-  float* dwk; long wsb;
-};
-
-__global__ __launch_bounds__(256, 1) void conv_split_wgrad_k(SplitWgradP p) {
-  constexpr int TX = 32, TY = 4, TZ = 2, TM = TX * TY * TZ;
-  constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HV = HX * HY * HZ;
-  constexpr int PR = 64;                                // LDS row pitch (bytes): 32 bf16 channels
-  constexpr int HIT = (HV * 8 + 255) / 256, DIT = TM * 8 / 256, NIT = HIT + DIT;      // 16-byte fp32 pieces per thread
-  constexpr int MAXT = 7;                               // taps per wave
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Gh = smem;                                      // [HV][64] x hi
-  char* Gl = Gh + HV * PR;                              //          x lo
-  char* Dh = Gl + HV * PR;                              // [TM][64] dy hi
-  char* Dl = Dh + TM * PR;                              //          dy lo
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.z;
-  const int n0 = (blockIdx.y / p.cblocks) * 32, c0 = (blockIdx.y % p.cblocks) * 32;
-  const float* dnb = p.dy + (long)b * p.sbd + n0;
-  const float* gab = p.x + (long)b * p.sbg + c0;
-  const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, p.gbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, p.dbytes, 0x00020000);
-  constexpr unsigned OOB = 0x7fff0000u;
-
-  // staging: piece = tid + 256 it -> (row = piece >> 3, 4-channel piece = tid & 7); positions relative to the tile origin - 1.
-  // A piece past the tensor's channels (partial 32-channel block) reads as zero: it never touches the neighbouring slice.
-  const int chq = (tid & 7) * 4;
-  const unsigned choff = (unsigned)(chq * 4);
-  const bool ch_g = c0 + chq < p.C, ch_d = n0 + chq < p.N;
-  int s_pos[NIT];                                       // packed z | y << 4 | x << 8
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    if (it < HIT) {
-      const int row = (tid + 256 * it) >> 3;
-      const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
-      s_pos[it] = row < HV ? (hz | (hy << 4) | (hx << 8)) : (15 | (15 << 4) | (1023 << 8));
-    } else {
-      const int row = (tid + 256 * (it - HIT)) >> 3;
-      s_pos[it] = ((row / (TY * 32)) + 1) | ((((row >> 5) % TY) + 1) << 4) | (((row & 31) + 1) << 8);
-    }
-  }
-  uint4 sreg[NIT];
-  auto issue_all = [&](int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rg, const __amdgpu_buffer_rsrc_t& rd) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int gz = z0 - 1 + (s_pos[it] & 15), gy = y0 - 1 + ((s_pos[it] >> 4) & 15), gx = x0 - 1 + (s_pos[it] >> 8);
-      const bool ok = (unsigned)gz < (unsigned)p.D && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W && (it < HIT ? ch_g : ch_d);
-      const unsigned off = (unsigned)(((gz * p.H + gy) * p.W + gx) * (it < HIT ? p.ldg : p.ldd)) * 4u + choff;
-      const auto v = __builtin_amdgcn_raw_buffer_load_b128(it < HIT ? rg : rd, ok ? off : OOB, 0, 0);
-      sreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
-    }
-  };
-  auto store_tile = [&]() __attribute__((always_inline)) {      // the split: one conversion per staged element
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      uint2 hi, lo;
-      split4(sreg[it], hi, lo);
-      if (it < HIT) {
-        const int piece = tid + 256 * it;
-        if ((piece >> 3) < HV) { *reinterpret_cast<uint2*>(Gh + piece * 8) = hi; *reinterpret_cast<uint2*>(Gl + piece * 8) = lo; }
-      } else {
-        const int piece = tid + 256 * (it - HIT);
-        *reinterpret_cast<uint2*>(Dh + piece * 8) = hi; *reinterpret_cast<uint2*>(Dl + piece * 8) = lo;
-      }
-    }
-  };
-
-  f32x16_t acc[MAXT];
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-  // per-wave tap list (wave-uniform): tap = wid + 4 t; byte offset of the tap's shift in the halo image
-  int toff_w[MAXT];
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) {
-    const int tap = wid + 4 * t;
-    const int kx = tap % 3, ky = (tap / 3) % 3, kz = tap / 9;
-    toff_w[t] = __builtin_amdgcn_readfirstlane(((kz * HY + ky) * HX + kx) * PR);
-  }
-  const bool last_tap = wid + 4 * (MAXT - 1) < 27;      // (wave 3 has six taps)
-  // lane roles of the transposed reads (as conv_mfma_wgrad_k): a 16-lane group covers 4 voxels x 16 channels per read
-  const int g16 = lane >> 4, li = lane & 15, q4 = li >> 2, pp = li & 3;
-  const int chan_b = ((g16 & 1) * 16 + 4 * pp) * 2;     // byte offset of this lane's 4 channels in the 32-channel row
-  const int vrow = 8 * (g16 >> 1) + q4;                 // voxel (within a 16-voxel K step) whose row this lane addresses
-
-  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
-  int id_end = id_begin + p.ids_per_block;
-  if (id_end > p.ids_total) id_end = p.ids_total;
-  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
-  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
-  if (id >= id_end) return;
-  issue_all(tiz * TZ, tiy * TY, tix * TX, rs_g, rs_d);
-  while (id < id_end) {
-    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
-    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
-    const bool has_next = nid < id_end;
-    const __amdgpu_buffer_rsrc_t rn_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gab), 0, has_next ? p.gbytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dnb), 0, has_next ? p.dbytes : 0, 0x00020000);
-    __syncthreads();
-    store_tile();
-    __syncthreads();
-    issue_all(ntiz * TZ, ntiy * TY, ntix * TX, rn_g, rn_d);
-    // 16 K steps of 16 voxels: step ks = half an x row of the tile
-#pragma unroll 2
-    for (int ks = 0; ks < TM / 16; ++ks) {
-      const int r = ks >> 1, xh = (ks & 1) * 16 + vrow;                      // dense row (z, y) of the tile, x within it
-      const int d1 = (r * 32 + xh) * PR + chan_b;
-      const int g1 = (((r / TY) * HY + (r % TY)) * HX + xh) * PR + chan_b;   // the same voxel in the halo image, tap (0, 0, 0)
-      auto frag = [&](const char* base) __attribute__((always_inline)) -> uint4 {
-        const s4_t u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base));
-        const s4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base + 4 * PR));
-        const bf16x8_t f = (bf16x8_t){u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
-        return *reinterpret_cast<const uint4*>(&f);
-      };
-      const uint4 dh = frag(Dh + d1), dl = frag(Dl + d1);
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (t < MAXT - 1 || last_tap) {
-          const uint4 gh = frag(Gh + g1 + toff_w[t]), gl = frag(Gl + g1 + toff_w[t]);
-          acc[t] = mma3(dh, dl, gh, gl, acc[t]);
-        }
-      }
-    }
-    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
-  }
-  // ---- merge into dwk[b][tap][n][c]: MFMA rows = n (A = dy), columns = c (B = x) ----
-  float* wout = p.dwk + (long)b * p.wsb;
-  const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) {
-    const int tap = wid + 4 * t;
-    if (tap < 27) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int n = n0 + (e & 3) + 8 * (e >> 2) + 4 * fh, c = c0 + fr;
-        if (n < p.N && c < p.C) atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, acc[t][e]);
-      }
-    }
-  }
-}
-
-// the problems conv_f32_wgrad16_k<1, 0> takes, plus partial 32-channel blocks (C, N multiples of 16)
-bool conv_split_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
-  return d->ksize == 3 && d->form == 0 && d->stride == 1 && d->pad == 1 && x->dtype == COMA_F32 && dy->dtype == COMA_F32 &&
-         t_same_grid(x, dy) && x->W >= 32 && x->C >= 32 && dy->C >= 32 && x->C % 16 == 0 && dy->C % 16 == 0 &&
-         x->ld % 4 == 0 && x->sb % 4 == 0 && dy->ld % 4 == 0 && dy->sb % 4 == 0 &&
-         (!x->data || aligned16(x->data)) && (!dy->data || aligned16(dy->data)) &&
-         (unsigned long long)t_vox(x) * x->ld * 4 < 0x7fff0000ull && (unsigned long long)t_vox(dy) * dy->ld * 4 < 0x7fff0000ull;
-}
-
-int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
-  COMA_CHECK(conv_split_wgrad_ok(d, x, dy), "conv_split_wgrad: problem not in the split kernel's scope");
-  SplitWgradP q;
-  q.dy = (const float*)dy->data; q.ldd = (int)dy->ld; q.sbd = dy->sb;
-  q.x = (const float*)x->data; q.ldg = (int)x->ld; q.sbg = x->sb;
-  q.D = x->D; q.H = x->H; q.W = x->W; q.N = dy->C; q.C = x->C;
-  // (descriptor ranges are measured from the block's channel offset; the voxel and channel tests keep every piece inside)
-  q.dbytes = (unsigned)((unsigned long long)t_vox(dy) * dy->ld * 4);
-  q.gbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
-  q.cblocks = (q.C + 31) / 32;
-  const int pairs = q.cblocks * ((q.N + 31) / 32);
-  int gx = 256 / (pairs * x->B);                       // one block per CU, one round: a second round repeats the atomic merge
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
-  const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
-  q.wsb = d->per_sample_w ? wsz1 : 0;
-  q.dwk = dwk;
-  if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
-  const size_t lds = (size_t)2 * (34 * 6 * 4 + 256) * 64;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_wgrad_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-  coma_set_kernel_tag("conv_split_wgrad_k");
-  hipLaunchKernelGGL(conv_split_wgrad_k, dim3((unsigned)gx, (unsigned)pairs, (unsigned)x->B), dim3(256), lds, s, q);
-  COMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// =====================================================================================
-// Wide split (coma_conv_desc.algo = 5): the stride-2 families.
-//   conv_split_tconv_k  -- stride-2 3x3x3 transposed convolution / data gradient of the stride-2 convolutions
-//                          (the problems of conv_mfma_tconv_k<float, *>)
-//   conv_split_wgrad2_k -- stride-2 and transposed 3x3x3 weight gradient (the problems of conv_f32_wgrad16_k<2, *>)
-// =====================================================================================
-bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));      // (native vectors for the staging registers: see conv_mfma_duo_k)
 
@@ -794,49 +594,54 @@ int conv_split_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* 
   q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
   q.wbytes = (unsigned)wb_;
   q.accum = accum;
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   const int nblk_n = y->C / 32;
-  int gx = 512 / (nblk_n * x->B);                      // one block per CU, about two rounds
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_split_tconv_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, nblk_n * x->B);      // one block per CU, about two rounds
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
+  set_max_lds<conv_split_tconv_k>();
   const size_t lds = (size_t)(33 * 5 * 3 + 14 * 32) * 80;
   coma_set_kernel_tag("conv_split_tconv_k");
-  const dim3 grid((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B);
-  hipLaunchKernelGGL(conv_split_tconv_k, grid, dim3(256), lds, s, q);
+  hipLaunchKernelGGL(conv_split_tconv_k, dim3((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B), dim3(256), lds, s, q);
   COMA_LAUNCH_CHECK();
   return 0;
 }
 
 // =====================================================================================
-// conv_split_wgrad2_k -- the frame of conv_f32_wgrad16_k<2, FORM> (a block owns a 32 x 32 (n, c) weight tile and a run of
-// 1 x 2 x 32-voxel DENSE tiles on the coarse grid with their 3 x 5 x 65 = 975-row GATHERED region on the fine grid) with
-// the MFMA body of conv_split_wgrad_k: four bf16 images (dense hi / lo, gathered hi / lo: 133 KB, the bytes of the fp32
-// images), voxels along K, operands read transposed with ds_read_b64_tr_b16, the 27 taps dealt to the 4 waves, fp32
-// accumulators kept over the block's tiles, fp32 atomic merge.  The stride lives in the lanes' row addresses: dense voxel
-// m of a row pairs with gathered row 2 m + tap.
-// FORM 0: stride-2 convolution (dense dy -> MFMA rows n, gathered x -> columns c);
+// conv_split_wgrad_k, conv_split_wgrad2_k<FORM> -- the 3x3x3 weight gradients: one body, split_wgrad_body<S, FORM>, behind
+// the two entry points.  dwk[b][tap][n][c] += sum_m dy[.][n] * x[.][c], the reduction index is the voxel m of the DENSE
+// operand's grid; dense voxel m pairs with GATHERED voxel S m + tap - 1.
+// The frame of conv_f32_wgrad16_k<S, FORM> (a block owns a 32 x 32 (n, c) weight tile and a run of dense tiles, 2 x 4 x 32
+// voxels at S = 1, 1 x 2 x 32 at S = 2; the dense tile and its gathered region, 4 x 6 x 34 = 816 rows / 3 x 5 x 65 = 975
+// rows, are staged by buffer loads, the next tile's pieces in flight while this one computes) with the MFMA body of
+// conv_mfma_wgrad_k<1, 1, 0>: both operands are [voxel][32 channels] bf16 images (64-byte rows) read transposed with
+// ds_read_b64_tr_b16, the 27 taps are dealt to the 4 waves (7, 7, 7, 6) whose 32 x 32 fp32 accumulators stay in registers
+// over the block's tiles and merge into dwk with fp32 atomics at the end.  Each image exists twice (hi, lo): together the
+// bytes of the fp32 images of conv_f32_wgrad16_k (134 KB / 133 KB).  The stride lives in the lanes' row addresses.
+// FORM 0: convolution (dense dy -> MFMA rows n, gathered x -> columns c); at S = 1 both operands lie on one grid.
 // FORM 1: transposed stride-2 convolution (dense x -> columns c, gathered dy -> rows n).
 // =====================================================================================
-struct SplitWgrad2P {
-  const float* dn; int ldd; long sbd; int Mz, My, Mx;      // dense operand on the coarse grid
-  const float* ga; int ldg; long sbg; int Gz, Gy, Gx;      // gathered operand on the fine grid
+struct SplitWgradP {
+  const float* dn; int ldd; long sbd; int Mz, My, Mx;      // dense operand (S = 2: on the coarse grid)
+  const float* ga; int ldg; long sbg; int Gz, Gy, Gx;      // gathered operand (S = 2: on the fine grid)
   int N, C;
   unsigned dbytes, gbytes;
   int ntx, nty, ntz, ids_total, ids_per_block, cblocks;
   float* dwk; long wsb;
 };
 
-template <int FORM>
-__global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
-  constexpr int TX = 32, TY = 2, TZ = 1, TM = TX * TY * TZ;
-  constexpr int HX = 2 * TX + 1, HY = 2 * TY + 1, HZ = 2 * TZ + 1, HV = HX * HY * HZ;      // 65 x 5 x 3
-  constexpr int PR = 64;                                // LDS row pitch (bytes): 32 bf16 channels
-  constexpr int HIT = (HV * 8 + 255) / 256, DIT = TM * 8 / 256, NIT = HIT + DIT;      // 16-byte fp32 pieces per thread: 31 + 2
+// tile constants shared by the body and its launcher
+template <int S> struct SplitWgradTile {
+  static constexpr int TX = 32, TY = S == 1 ? 4 : 2, TZ = S == 1 ? 2 : 1, TM = TX * TY * TZ;                     // dense tile
+  static constexpr int HX = S * (TX - 1) + 3, HY = S * (TY - 1) + 3, HZ = S * (TZ - 1) + 3, HV = HX * HY * HZ;   // gathered region
+  static constexpr int PR = 64;                         // LDS row pitch (bytes): 32 bf16 channels
+  static constexpr int LDS = 2 * (HV + TM) * PR;        // four images: gathered hi / lo, dense hi / lo
+};
+
+// (p by value: behind a reference the compiler no longer keeps the merge's tap * N * C address terms in scalar registers)
+template <int S, int FORM>
+__device__ __forceinline__ void split_wgrad_body(const SplitWgradP p) {
+  using T = SplitWgradTile<S>;
+  constexpr int TX = T::TX, TY = T::TY, TZ = T::TZ, TM = T::TM, HX = T::HX, HY = T::HY, HV = T::HV, PR = T::PR;
+  constexpr int HIT = (HV * 8 + 255) / 256, DIT = TM * 8 / 256, NIT = HIT + DIT;      // 16-byte fp32 pieces per thread: 26 + 8 / 31 + 2
   constexpr int MAXT = 7;                               // taps per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Gh = smem;                                      // [HV][64] gathered hi
@@ -856,8 +661,8 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
   constexpr unsigned OOB = 0x7fff0000u;
 
   // staging: piece = tid + 256 it -> (row = piece >> 3, 4-channel piece = tid & 7); gathered positions relative to
-  // 2 * tile origin - 1, dense positions relative to the tile origin - 1.  A piece outside its volume or past the tensor's
-  // channels reads as zero.
+  // S * tile origin - 1, dense positions relative to the tile origin - 1.  A piece outside its volume or past the tensor's
+  // channels (partial 32-channel block) reads as zero: it never touches the neighbouring slice.
   const int chq = (tid & 7) * 4;
   const unsigned choff = (unsigned)(chq * 4);
   const bool ch_g = gch0 + chq < gchn, ch_d = dch0 + chq < dchn;
@@ -877,7 +682,7 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
   auto issue_all = [&](int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rg, const __amdgpu_buffer_rsrc_t& rd) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int sc = it < HIT ? 2 : 1;
+      const int sc = it < HIT ? S : 1;
       const int gz = sc * z0 - 1 + (s_pos[it] & 15), gy = sc * y0 - 1 + ((s_pos[it] >> 4) & 15), gx = sc * x0 - 1 + (s_pos[it] >> 8);
       const bool ok = it < HIT ? ((unsigned)gz < (unsigned)p.Gz && (unsigned)gy < (unsigned)p.Gy && (unsigned)gx < (unsigned)p.Gx && ch_g)
                                : ((unsigned)gz < (unsigned)p.Mz && (unsigned)gy < (unsigned)p.My && (unsigned)gx < (unsigned)p.Mx && ch_d);
@@ -916,7 +721,7 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
     toff_w[t] = __builtin_amdgcn_readfirstlane(((kz * HY + ky) * HX + kx) * PR);
   }
   const bool last_tap = wid + 4 * (MAXT - 1) < 27;      // (wave 3 has six taps)
-  // lane roles of the transposed reads (as conv_split_wgrad_k): a 16-lane group covers 4 voxels x 16 channels per read
+  // lane roles of the transposed reads (as conv_mfma_wgrad_k): a 16-lane group covers 4 voxels x 16 channels per read
   const int g16 = lane >> 4, li = lane & 15, q4 = li >> 2, pp = li & 3;
   const int chan_b = ((g16 & 1) * 16 + 4 * pp) * 2;     // byte offset of this lane's 4 channels in the 32-channel row
   const int vrow = 8 * (g16 >> 1) + q4;                 // voxel (within a 16-voxel K step) whose row this lane addresses
@@ -938,12 +743,13 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
     store_tile();
     __syncthreads();
     issue_all(ntiz * TZ, ntiy * TY, ntix * TX, rn_g, rn_d);
-    // 4 K steps of 16 dense voxels: step ks = half an x row of the tile
-#pragma unroll
+    // TM / 16 K steps of 16 dense voxels (16 steps at S = 1, unrolled by 2; 4 at S = 2, unrolled): step ks = half an x row
+    constexpr int KUNROLL = S == 1 ? 2 : TM / 16;
+#pragma unroll KUNROLL
     for (int ks = 0; ks < TM / 16; ++ks) {
-      const int r = ks >> 1, xh = (ks & 1) * 16 + vrow;                      // dense row y of the tile, x within it
+      const int r = ks >> 1, xh = (ks & 1) * 16 + vrow;                      // dense row (z, y) of the tile, x within it
       const int d1 = (r * 32 + xh) * PR + chan_b;
-      const int g1 = ((2 * r) * HX + 2 * xh) * PR + chan_b;                  // the same voxel's tap (0, 0, 0) in the gathered image
+      const int g1 = (((S * (r / TY)) * HY + S * (r % TY)) * HX + S * xh) * PR + chan_b;   // the same voxel's tap (0, 0, 0) in the gathered image
       auto frag = [&](const char* base, int step) __attribute__((always_inline)) -> uint4 {
         const s4_t u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base));
         const s4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(base + step));
@@ -954,7 +760,7 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
         if (t < MAXT - 1 || last_tap) {
-          const uint4 gh = frag(Gh + g1 + toff_w[t], 8 * PR), gl = frag(Gl + g1 + toff_w[t], 8 * PR);
+          const uint4 gh = frag(Gh + g1 + toff_w[t], 4 * S * PR), gl = frag(Gl + g1 + toff_w[t], 4 * S * PR);
           acc[t] = FORM == 0 ? mma3(dh, dl, gh, gl, acc[t]) : mma3(gh, gl, dh, dl, acc[t]);
         }
       }
@@ -977,6 +783,20 @@ __global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgrad2P p) {
   }
 }
 
+__global__ __launch_bounds__(256, 1) void conv_split_wgrad_k(SplitWgradP p) { split_wgrad_body<1, 0>(p); }
+
+template <int FORM>
+__global__ __launch_bounds__(256, 1) void conv_split_wgrad2_k(SplitWgradP p) { split_wgrad_body<2, FORM>(p); }
+
+// the problems conv_f32_wgrad16_k<1, 0> takes, plus partial 32-channel blocks (C, N multiples of 16)
+bool conv_split_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  return d->ksize == 3 && d->form == 0 && d->stride == 1 && d->pad == 1 && x->dtype == COMA_F32 && dy->dtype == COMA_F32 &&
+         t_same_grid(x, dy) && x->W >= 32 && x->C >= 32 && dy->C >= 32 && x->C % 16 == 0 && dy->C % 16 == 0 &&
+         x->ld % 4 == 0 && x->sb % 4 == 0 && dy->ld % 4 == 0 && dy->sb % 4 == 0 &&
+         (!x->data || aligned16(x->data)) && (!dy->data || aligned16(dy->data)) &&
+         (unsigned long long)t_vox(x) * x->ld * 4 < 0x7fff0000ull && (unsigned long long)t_vox(dy) * dy->ld * 4 < 0x7fff0000ull;
+}
+
 bool conv_split_wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   const coma_tensor* dn = d->form == 0 ? dy : x;
   const coma_tensor* ga = d->form == 0 ? x : dy;
@@ -985,41 +805,42 @@ bool conv_split_wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const c
          ga->D <= 2 * dn->D && ga->H <= 2 * dn->H && ga->W <= 2 * dn->W;
 }
 
-int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
-  COMA_CHECK(conv_split_wgrad2_ok(d, x, dy), "conv_split_wgrad2: problem not in the split kernel's scope");
+template <int S, auto KERNEL>
+static int launch_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
+  using T = SplitWgradTile<S>;
   const coma_tensor* dn = d->form == 0 ? dy : x;
   const coma_tensor* ga = d->form == 0 ? x : dy;
-  SplitWgrad2P q;
+  SplitWgradP q;
   q.dn = (const float*)dn->data; q.ldd = (int)dn->ld; q.sbd = dn->sb; q.Mz = dn->D; q.My = dn->H; q.Mx = dn->W;
   q.ga = (const float*)ga->data; q.ldg = (int)ga->ld; q.sbg = ga->sb; q.Gz = ga->D; q.Gy = ga->H; q.Gx = ga->W;
   q.N = dy->C; q.C = x->C;
   // (descriptor ranges are measured from the block's channel offset; the voxel and channel tests keep every piece inside)
   q.dbytes = (unsigned)((unsigned long long)t_vox(dn) * dn->ld * 4);
   q.gbytes = (unsigned)((unsigned long long)t_vox(ga) * ga->ld * 4);
-  q.ntx = (q.Mx + 31) / 32; q.nty = (q.My + 1) / 2; q.ntz = q.Mz;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   q.cblocks = (q.C + 31) / 32;
   const int pairs = q.cblocks * ((q.N + 31) / 32);
-  int gx = 256 / (pairs * x->B);                       // one block per CU, one round: a second round repeats the atomic merge
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  // one block per CU, one round: a second round repeats the atomic merge
+  const TileRun r = tile_run(q.Mz, q.My, q.Mx, T::TX, T::TY, T::TZ, 256, pairs * x->B);
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
   q.dwk = dwk;
   if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
-  const size_t lds = (size_t)2 * (65 * 5 * 3 + 64) * 64;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_split_wgrad2_k<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_split_wgrad2_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  const dim3 grid((unsigned)gx, (unsigned)pairs, (unsigned)x->B);
-  coma_set_kernel_tag("conv_split_wgrad2_k<%d>", d->form);
-  if (d->form == 0) hipLaunchKernelGGL(conv_split_wgrad2_k<0>, grid, dim3(256), lds, s, q);
-  else hipLaunchKernelGGL(conv_split_wgrad2_k<1>, grid, dim3(256), lds, s, q);
+  set_max_lds<KERNEL>();
+  if (S == 1) coma_set_kernel_tag("conv_split_wgrad_k");
+  else coma_set_kernel_tag("conv_split_wgrad2_k<%d>", d->form);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)r.gx, (unsigned)pairs, (unsigned)x->B), dim3(256), (size_t)T::LDS, s, q);
   COMA_LAUNCH_CHECK();
   return 0;
+}
+
+int conv_split_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
+  COMA_CHECK(conv_split_wgrad_ok(d, x, dy), "conv_split_wgrad: problem not in the split kernel's scope");
+  return launch_split_wgrad<1, conv_split_wgrad_k>(d, x, dy, dwk, s, zeroed);
+}
+
+int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed) {
+  COMA_CHECK(conv_split_wgrad2_ok(d, x, dy), "conv_split_wgrad2: problem not in the split kernel's scope");
+  return d->form == 0 ? launch_split_wgrad<2, conv_split_wgrad2_k<0>>(d, x, dy, dwk, s, zeroed)
+                      : launch_split_wgrad<2, conv_split_wgrad2_k<1>>(d, x, dy, dwk, s, zeroed);
 }

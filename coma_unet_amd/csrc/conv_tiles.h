@@ -1,6 +1,22 @@
-// Device helpers shared by the halo-tiled convolution kernels (conv_mfma.hip, conv_split.hip).
+// Helpers shared by the halo-tiled convolution kernels (conv_mfma.hip, conv_split.hip).
 #pragma once
 #include "common.h"
+
+// Host side: the launch of a persistent tile-run kernel.  A D x H x W grid in tz x ty x tx tiles gives ids_total tile ids
+// (tile_coords below; padded to 8 z-tiles); the x dimension of the launch gets what is left of a budget of blocks after
+// the blocks_yz blocks of the other two dimensions, each block walking ids_per_block consecutive ids.
+struct TileRun { int ntx, nty, ntz, ids_total, ids_per_block, gx; };
+static inline TileRun tile_run(int D, int H, int W, int tx, int ty, int tz, int budget_blocks, int blocks_yz) {
+  TileRun r;
+  r.ntx = (W + tx - 1) / tx; r.nty = (H + ty - 1) / ty; r.ntz = (D + tz - 1) / tz;
+  r.ids_total = r.ntx * r.nty * ((r.ntz + 7) / 8) * 8;
+  r.gx = budget_blocks / blocks_yz;
+  if (r.gx < 1) r.gx = 1;
+  if (r.gx > r.ids_total) r.gx = r.ids_total;
+  r.ids_per_block = (r.ids_total + r.gx - 1) / r.gx;
+  r.gx = (r.ids_total + r.ids_per_block - 1) / r.ids_per_block;      // (no block without an id)
+  return r;
+}
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // 8 bf16 = one MFMA A/B fragment
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;  // 32x32 accumulator fragment

@@ -15,18 +15,13 @@ Two checks per case:
     (tests/test_split_cpu.py): a correct split is 4.4e-6 (22x below), one that drops a cross term is 1.66e-3 (16x above).
     The exact-fp32 kernels (algo = 0) are held to the same assertion as the control.
 """
-import gc
-import zlib
-
 import pytest
 import torch
 
 from oracle import fp64_ref as R
+from _split_abi import SLAB_TOL, _buf, _check, _free, _gen, _ops, _rand, _weights
 
 pytestmark = pytest.mark.gpu
-
-SLAB_TOL = 1e-4
-SPLIT_TERM = 2.0 ** -14
 
 # (B, D, H, W, Cin, Cout, x pitch, y pitch): small enough for a CPU-side fp64 reference in seconds, each crossing a tile edge
 # (tiles are 2 x 4 x 32 voxels, 32 output channels, 16-channel chunks)
@@ -37,42 +32,6 @@ CASES = [
     (1, 3, 9, 33, 32, 48, 64, 64),      # both sides channel slices of wider buffers, N not a multiple of 32
 ]
 _ids = lambda c: "x".join(str(v) for v in c)
-
-
-def _ops():
-    from coma_unet_amd import ops, _lib
-    return ops, _lib
-
-
-def _buf(shape, ld, fill):
-    """A (B, D, H, W, C) fp32 view with voxel pitch ld >= C whose foreign lanes hold `fill`."""
-    C = shape[-1]
-    b = torch.full(tuple(shape[:-1]) + (max(ld, C),), fill, dtype=torch.float32, device="cuda")
-    return b[..., :C]
-
-
-def _rand(shape, ld, gen, scale=1.0):
-    v = _buf(shape, ld, 3.0e4)        # (finite garbage in the foreign lanes: a kernel that reads them is far off)
-    v.copy_(torch.randn(tuple(shape), generator=gen, device="cuda") * scale)
-    return v
-
-
-def _weights(Bw, cout, cin, gen):
-    """Gaussian fp32 kernel-layout weights wk[Bw, 27, Cout, Cin], outputs O(1)."""
-    return (torch.randn((Bw, 27, cout, cin), generator=gen, device="cuda") * (1.0 / (27 * cin) ** 0.5)).contiguous()
-
-
-def _gen(*key):
-    return torch.Generator(device="cuda").manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _bound(ref, A, K):
-    return R.elem_bound(ref, A, 3 * K, u_out=R.U_F32) + SPLIT_TERM * A
-
-
-def _free():
-    gc.collect()
-    torch.cuda.empty_cache()
 
 
 def _tensors(case):
@@ -135,14 +94,6 @@ def _wgrad(case, ps, algo, key):
 
 
 _RUN = {"fwd": lambda c, ps, a, k: _fwd(c, ps, a, None, False, k), "dgrad": _dgrad, "wgrad": _wgrad}
-
-
-def _check(r, what):
-    ratio = R.check_elementwise(r["y"], r["ref"], _bound(r["ref"], r["A"], r["K"]), what)
-    slab = R.slab_rel_l2(r["y"], r["ref"], 2)
-    print(f"{what}: kernel {r['kernel']}, worst ratio to the element bound {ratio:.3g}, max slab rel-L2 {slab:.3g}")
-    assert slab <= SLAB_TOL, (what, slab)
-    return ratio, slab
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -7,25 +7,20 @@ split, through the C ABI against the fp64 references of oracle/fp64_ref.py.
   twgrad -- weight gradient of a transposed stride-2 convolution               conv_split_wgrad2_k<1>
 
 Helpers, operands (Gaussian fp32, not bf16-exact; finite garbage in foreign lanes) and the two checks (per-element bound
-elem_bound(ref, A, 3K, 2^-24) + 2^-14 A; max slab rel-L2 <= 1e-4) are those of test_conv_split_gpu.py; the exact kernels
-(algo = 0) run through the same assertions as the control.
+elem_bound(ref, A, 3K, 2^-24) + 2^-14 A; max slab rel-L2 <= 1e-4) are those of test_conv_split_gpu.py, shared through
+tests/_split_abi.py; the exact kernels (algo = 0) run through the same assertions as the control.
 
 A case is (B, coarse D, H, W, coarse channels, fine channels, coarse pitch, fine pitch, odd): the coarse grid is the dense
 side (tiles of 2 x 4 x 32 voxels for the transposed kernel, 1 x 2 x 32 for the weight gradients), the fine grid is
 2 x coarse, or 2 x coarse - 1 with `odd` for the two operations whose fine side is a convolution's INPUT (dgrad, wgrad).
 """
-import gc
-import zlib
-
 import pytest
 import torch
 
 from oracle import fp64_ref as R
+from _split_abi import SLAB_TOL, _buf, _check, _free, _gen, _ops, _rand, _weights
 
 pytestmark = pytest.mark.gpu
-
-SLAB_TOL = 1e-4
-SPLIT_TERM = 2.0 ** -14
 
 CASES = [
     (2, 3, 5, 33, 64, 32, 64, 32, False),
@@ -38,40 +33,6 @@ WHATS = ["tfwd", "dgrad", "wgrad", "twgrad"]
 NEW = {"tfwd": "conv_split_tconv_k", "dgrad": "conv_split_tconv_k", "wgrad": "conv_split_wgrad2_k<0>", "twgrad": "conv_split_wgrad2_k<1>"}
 OLD = {"tfwd": "conv_mfma_tconv_k<float", "dgrad": "conv_mfma_tconv_k<float", "wgrad": "conv_f32_wgrad16_k<2, 0>",
        "twgrad": "conv_f32_wgrad16_k<2, 1>"}
-
-
-def _ops():
-    from coma_unet_amd import ops, _lib
-    return ops, _lib
-
-
-def _buf(shape, ld, fill):
-    C = shape[-1]
-    b = torch.full(tuple(shape[:-1]) + (max(ld, C),), fill, dtype=torch.float32, device="cuda")
-    return b[..., :C]
-
-
-def _rand(shape, ld, gen, scale=1.0):
-    v = _buf(shape, ld, 3.0e4)        # (finite garbage in the foreign lanes: a kernel that reads them is far off)
-    v.copy_(torch.randn(tuple(shape), generator=gen, device="cuda") * scale)
-    return v
-
-
-def _weights(Bw, cout, cin, gen):
-    return (torch.randn((Bw, 27, cout, cin), generator=gen, device="cuda") * (1.0 / (27 * cin) ** 0.5)).contiguous()
-
-
-def _gen(*key):
-    return torch.Generator(device="cuda").manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _bound(ref, A, K, base=None):
-    return R.elem_bound(ref, A, 3 * K, u_out=R.U_F32, base=base) + SPLIT_TERM * A
-
-
-def _free():
-    gc.collect()
-    torch.cuda.empty_cache()
 
 
 def _grids(case, fine_is_input):
@@ -152,14 +113,6 @@ def _wgrad(case, ps, algo, key, transposed=False):
 
 
 _RUN = {"tfwd": _tfwd, "dgrad": _dgrad, "wgrad": _wgrad, "twgrad": lambda c, ps, a, k: _wgrad(c, ps, a, k, True)}
-
-
-def _check(r, what):
-    ratio = R.check_elementwise(r["y"], r["ref"], _bound(r["ref"], r["A"], r["K"], r.get("base")), what)
-    slab = R.slab_rel_l2(r["y"], r["ref"], 2)
-    print(f"{what}: kernel {r['kernel']}, worst ratio to the element bound {ratio:.3g}, max slab rel-L2 {slab:.3g}")
-    assert slab <= SLAB_TOL, (what, slab)
-    return ratio, slab
 
 
 # ---------------------------------------------------------------------------------------------------------------------
