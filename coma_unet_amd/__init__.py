@@ -6,6 +6,7 @@ of ``include/coma_unet.h``) and raises if it is missing: there is no CPU/PyTorch
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is absent)
 from .attn_unet_data_parallel import (ContrastiveAttentionUNET_DP, ObservableAttentionUnet, AttentionLayer,
                                       ObservableAttentionBlock, UpBlock, ProjectionHead, StackedFusionConvLayers)
+from .inference import Predictor, fold_gate
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, build_reference_criterion
 
 DEFAULT_MODEL_PARAMS = (3, 1, 1, [32, 64, 128, 256, 512], [2] * 5)   # validation.py:727

@@ -104,6 +104,14 @@ class ObservableAttentionBlock(nn.Module):
             if self.save_attn:
                 return att, psi
             return att
+        if not self.training and cfg.eval_fused and getattr(self, "_eval_fold", None) is not None:
+            # inference: every BatchNorm is a known affine map, folded once (inference.fold_gate) -- the whole gate is one
+            # launch (bf16, C <= 64: W_g / W_x included), or one launch behind the two convolutions
+            from .inference import gate_eval
+            att, psi = gate_eval(self, g, x, out=out, want_psi=bool(self.save_attn))
+            if self.save_attn:
+                return att, psi
+            return att
         g1 = conv_then_bn(cfg, g, self.W_g[0], self.W_g[1], L.ACT_NONE, self.training)
         x1 = conv_then_bn(cfg, x, self.W_x[0], self.W_x[1], L.ACT_NONE, self.training)
         s = ops.AddRelu.apply(g1, x1)
@@ -365,7 +373,7 @@ class ContrastiveAttentionUNET_DP(ObservableAttentionUnet):
         # a configuration records which layers prepare what)
         if covariate is not None and covariate.dim() == 3 and x.is_cuda:
             ops.PrepAhead.begin(self, (tuple(x.shape), x.dtype, self.cfg.compute_dtype, self.training, torch.is_grad_enabled(),
-                                       bool(x.requires_grad), self.static_prompts), x.device, covariate, x.shape[0])
+                                       bool(x.requires_grad), self.static_prompts, bool(self.cfg.eval_fused)), x.device, covariate, x.shape[0])
         ok = False
         try:
             res = self._forward(x, xi, covariate, roi_pred_dicts, sample_roi_mask)

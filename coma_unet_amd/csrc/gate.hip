@@ -13,7 +13,13 @@
 //   gate_mid_bwd_partial_k / _apply_k: dz -> d(psi_raw) -> ds -> relu mask -> the two BatchNorm backwards at once (they
 //   share d(s)), d(w_psi) and every parameter gradient; only dg1raw / dx1raw are written.
 // All BatchNorms are training-mode with statistics records (norm_common.h); R = B * V elements per channel.
+//
+// EVAL mode (inference): every BatchNorm is a known affine map the host folds once into fp32 tables, so the gate is one pass
+//     att = x * sigmoid(a_p * (w_psi . relu(scale_g * g1raw + scale_x * x1raw + shift)) + b_p)
+//   gate_eval_fwd_k   g1raw, x1raw, x -> att (, psi): ONE launch behind the W_g / W_x convolutions instead of six
+//   gate_eval_mfma_k  g, x -> att (, psi): both 1x1x1 convolutions on the bf16 MFMA included; s, g1, x1, psi_raw never exist
 #include "norm_common.h"
+#include "conv_tiles.h"   // bf16x8_t / f32x16_t
 
 struct GateMidP {
   const void* g1; int64_t ldg, sbg;
@@ -597,6 +603,243 @@ extern "C" int coma_gate_mid_bwd(const coma_tensor* dz, const coma_tensor* psi_r
   p.cv = F / vec;
   dim3 grid(gate_blocks(p.V * p.cv, 256 * 2, 4096), g1->B);
   GATE_DISPATCH(gate_mid_bwd_apply_k, g1->dtype, vec, grid, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Eval-mode gate.  The tables are folded by the host (coma_unet_amd/inference.py: fold_gate).
+struct GateEvalP {
+  const void* x; int64_t ldx, sbx;         // [B][V][C]
+  const void* g1; int64_t ldg, sbg;        // element-wise: g1raw [B][V][F];  MFMA: g [B][V][C]
+  const void* x1; int64_t ldx1, sbx1;      // element-wise: x1raw [B][V][F]
+  void* att; int64_t lda, sba;             // [B][V][C], possibly a channel slice
+  void* psi; int64_t ldq, sbq;             // [B][V][1] or NULL
+  int64_t V; int B, C, F, cv;
+  const float *scg, *scx, *sh, *w, *ab;    // scale_g[F], scale_x[F], shift[F], w_psi[F], {a_p, b_p}
+  const void *wg, *wx;                     // MFMA: folded bf16 weights [32][C], zero rows beyond F
+};
+
+// `cv` = max(C, F) / VEC lanes per voxel; the lanes with c0 < F form the dot product, those with c0 < C the multiply
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gate_eval_fwd_k(GateEvalP p) {
+  __shared__ float t_scg[GATE_TAB], t_scx[GATE_TAB], t_sh[GATE_TAB], t_w[GATE_TAB];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  for (int c = tid; c < p.F; c += 256) { t_scg[c] = p.scg[c]; t_scx[c] = p.scx[c]; t_sh[c] = p.sh[c]; t_w[c] = p.w[c]; }
+  __syncthreads();
+  const int cv = p.cv;                                   // a power of two <= 64
+  const int c0 = (tid % cv) * VEC;
+  const bool in_f = c0 < p.F, in_c = c0 < p.C;           // (F and C are multiples of VEC)
+  float scg[VEC], scx[VEC], sh[VEC], w[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    scg[j] = in_f ? t_scg[c0 + j] : 0.f; scx[j] = in_f ? t_scx[c0 + j] : 0.f;
+    sh[j] = in_f ? t_sh[c0 + j] : 0.f; w[j] = in_f ? t_w[c0 + j] : 0.f;
+  }
+  const float pa = p.ab[0], pb = p.ab[1];
+  const T* gb = reinterpret_cast<const T*>(p.g1) + (int64_t)b * p.sbg;
+  const T* x1b = reinterpret_cast<const T*>(p.x1) + (int64_t)b * p.sbx1;
+  const T* xb = reinterpret_cast<const T*>(p.x) + (int64_t)b * p.sbx;
+  T* ab = reinterpret_cast<T*>(p.att) + (int64_t)b * p.sba;
+  T* qb = p.psi ? reinterpret_cast<T*>(p.psi) + (int64_t)b * p.sbq : nullptr;
+  const int vpb = 256 / cv;                              // voxels per block step
+  const int64_t vstep = (int64_t)gridDim.x * vpb;
+  constexpr int U = 2;
+  for (int64_t v = (int64_t)blockIdx.x * vpb + tid / cv; v < p.V; v += U * vstep) {   // (whole waves run every trip: shuffles)
+    float gv[U][VEC], x1v[U][VEC], xv[U][VEC];
+    bool live[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t vv = v + u * vstep;
+      live[u] = vv < p.V;
+      const int64_t va = live[u] ? vv : v;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) { gv[u][j] = 0.f; x1v[u][j] = 0.f; xv[u][j] = 0.f; }
+      if (in_f) { vec_io<T, VEC>::load(gb + va * p.ldg + c0, gv[u]); vec_io<T, VEC>::load(x1b + va * p.ldx1 + c0, x1v[u]); }
+      if (in_c) vec_io<T, VEC>::load(xb + va * p.ldx + c0, xv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t vv = v + u * vstep;
+      float dot = 0.f;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float t = fmaf(gv[u][j], scg[j], fmaf(x1v[u][j], scx[j], sh[j]));
+        dot = fmaf(t > 0.f ? t : 0.f, w[j], dot);
+      }
+      for (int o = cv >> 1; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+      const T q = static_cast<T>(1.f / (1.f + expf(-fmaf(dot, pa, pb))));
+      const float ps = static_cast<float>(q);            // the stored psi, as the training kernels multiply with
+      if (live[u]) {
+        if (qb && c0 == 0) qb[vv * p.ldq] = q;
+        if (in_c) {
+          float ov[VEC];
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) ov[j] = xv[u][j] * ps;
+          vec_io<T, VEC>::store(ab + vv * p.lda + c0, ov);
+        }
+      }
+    }
+  }
+}
+
+// The whole gate in one launch, modelled on conv_mfma_pw_k (conv_mfma.hip): no LDS; the folded weights diag(scale) W of both
+// convolutions stay in registers as MFMA A fragments; a wave owns 32 voxels, lane (fr = lane & 31, fh = lane >> 5) streams
+// the 16-byte chunks [16 ks + 8 fh, + 8) of voxel fr of g and of x into the B operand, and both products land in ONE
+// accumulator (2 KS MFMAs).  The lane then holds rows 8 g4 + 4 fh + q (g4, q < 4) of its voxel's column: shift, ReLU and
+// the w_psi product over those 16 rows, one exchange with lane ^ 32 for the other 16, sigmoid -- and att = x * psi from
+// the x fragments it still holds (the two half-waves together own all C = 16 KS channels of the voxel), 16-byte stores.
+// The host pads the folded weights ([32][C]) and the shift / w_psi tables ([32]) with zero rows beyond F: relu(0 + 0) * 0,
+// those rows contribute exactly nothing and the kernel needs no F.
+template <int KS>
+__global__ __launch_bounds__(256) void gate_eval_mfma_k(GateEvalP p) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int fr = lane & 31, fh = lane >> 5;
+  const int b = blockIdx.y;
+  const bf16_t* gb = reinterpret_cast<const bf16_t*>(p.g1) + (int64_t)b * p.sbg;
+  const bf16_t* xb = reinterpret_cast<const bf16_t*>(p.x) + (int64_t)b * p.sbx;
+  bf16_t* ab = reinterpret_cast<bf16_t*>(p.att) + (int64_t)b * p.sba;
+  bf16_t* qb = p.psi ? reinterpret_cast<bf16_t*>(p.psi) + (int64_t)b * p.sbq : nullptr;
+  const bf16_t* wg = reinterpret_cast<const bf16_t*>(p.wg);
+  const bf16_t* wx = reinterpret_cast<const bf16_t*>(p.wx);
+  bf16x8_t wgf[KS], wxf[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int c = ks * 16 + fh * 8;                      // < C = 16 KS
+    const uint4 a = *reinterpret_cast<const uint4*>(wg + fr * p.C + c);
+    const uint4 c4 = *reinterpret_cast<const uint4*>(wx + fr * p.C + c);
+    wgf[ks] = *reinterpret_cast<const bf16x8_t*>(&a);
+    wxf[ks] = *reinterpret_cast<const bf16x8_t*>(&c4);
+  }
+  float sh[16], w[16];
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = 8 * g4 + 4 * fh + q;
+      sh[g4 * 4 + q] = p.sh[n];
+      w[g4 * 4 + q] = p.w[n];
+    }
+  const float pa = p.ab[0], pb = p.ab[1];
+  const int64_t mtiles = (p.V + 31) / 32;
+  for (int64_t mt = (int64_t)blockIdx.x * 4 + wid; mt < mtiles; mt += (int64_t)gridDim.x * 4) {
+    const int64_t v = mt * 32 + fr;
+    const bool live = v < p.V;
+    uint4 gq[KS], xq[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int c = ks * 16 + fh * 8;
+      gq[ks] = make_uint4(0, 0, 0, 0); xq[ks] = make_uint4(0, 0, 0, 0);
+      if (live) {
+        gq[ks] = *reinterpret_cast<const uint4*>(gb + v * p.ldg + c);
+        xq[ks] = *reinterpret_cast<const uint4*>(xb + v * p.ldx + c);
+      }
+    }
+    f32x16_t acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wgf[ks], *reinterpret_cast<const bf16x8_t*>(&gq[ks]), acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wxf[ks], *reinterpret_cast<const bf16x8_t*>(&xq[ks]), acc, 0, 0, 0);
+    }
+    float dot = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float t = acc[e] + sh[e];
+      dot = fmaf(t > 0.f ? t : 0.f, w[e], dot);
+    }
+    dot += __shfl_xor(dot, 32, 64);                      // (every lane of the wave is here: `live` only masks memory)
+    const bf16_t q = static_cast<bf16_t>(1.f / (1.f + expf(-fmaf(dot, pa, pb))));
+    const float ps = static_cast<float>(q);
+    if (live) {
+      if (qb && fh == 0) qb[v * p.ldq] = q;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const unsigned u[4] = {xq[ks].x, xq[ks].y, xq[ks].z, xq[ks].w};
+        bf16_t o[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[2 * j] = static_cast<bf16_t>(__uint_as_float(u[j] << 16) * ps);
+          o[2 * j + 1] = static_cast<bf16_t>(__uint_as_float(u[j] & 0xffff0000u) * ps);
+        }
+        *reinterpret_cast<uint4*>(ab + v * p.lda + ks * 16 + fh * 8) = *reinterpret_cast<const uint4*>(o);
+      }
+    }
+  }
+}
+
+static int gate_eval_common(GateEvalP& p, const coma_tensor* x, const coma_tensor* psi, const coma_tensor* att) {
+  p.x = x->data; p.ldx = x->ld; p.sbx = x->sb;
+  p.att = att->data; p.lda = att->ld; p.sba = att->sb;
+  p.psi = nullptr; p.ldq = 0; p.sbq = 0;
+  if (psi) { p.psi = psi->data; p.ldq = psi->ld; p.sbq = psi->sb; }
+  p.V = t_vox(x); p.B = x->B; p.C = x->C;
+  return 0;
+}
+
+extern "C" int coma_gate_eval_fwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw, const float* scale_g,
+                                  const float* scale_x, const float* shift, const float* w_psi, const float* psi_ab,
+                                  const coma_tensor* psi, const coma_tensor* att, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COMA_CHECK(x && g1raw && x1raw && att && x->data && g1raw->data && x1raw->data && att->data && scale_g && scale_x && shift &&
+             w_psi && psi_ab && (!psi || psi->data), "gate_eval_fwd: null argument");
+  COMA_CHECK(t_same_grid(x, g1raw) && t_same_grid(x, x1raw) && t_same_grid(x, att) && (!psi || (t_same_grid(x, psi) && psi->C == 1)) &&
+             g1raw->C == x1raw->C && x->C == att->C && x->dtype == g1raw->dtype && x->dtype == x1raw->dtype &&
+             x->dtype == att->dtype && (!psi || psi->dtype == x->dtype), "gate_eval_fwd: shape/dtype mismatch");
+  const int F = g1raw->C, C = x->C;
+  COMA_CHECK(F >= 1 && F <= GATE_TAB, "gate_eval_fwd: F=%d too large", F);
+  const coma_tensor* ts[4] = {x, g1raw, x1raw, att};
+  const int m = C > F ? C : F;
+  int vec = gate_vec(ts, 4, x->dtype == COMA_BF16 ? 8 : 4);
+  if (vec == 2) vec = 1;
+  while (vec > 1 && !pow2_le64(m / vec)) vec = vec == 8 ? 4 : 1;
+  COMA_CHECK(C % vec == 0 && F % vec == 0 && pow2_le64(m / vec),
+             "gate_eval_fwd: C=%d F=%d unsupported (max(C, F) / vector width must be a power of two <= 64)", C, F);
+  GateEvalP p{};
+  gate_eval_common(p, x, psi, att);
+  p.g1 = g1raw->data; p.ldg = g1raw->ld; p.sbg = g1raw->sb; p.x1 = x1raw->data; p.ldx1 = x1raw->ld; p.sbx1 = x1raw->sb;
+  p.F = F; p.cv = m / vec;
+  p.scg = scale_g; p.scx = scale_x; p.sh = shift; p.w = w_psi; p.ab = psi_ab;
+  int cap = 2048 / x->B; if (cap < 1) cap = 1;
+  dim3 grid(gate_blocks(p.V, (256 / p.cv) * 2, cap), x->B);
+  GATE_DISPATCH(gate_eval_fwd_k, x->dtype, vec, grid, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+static bool gate_al16(const coma_tensor* t) { return t->ld % 8 == 0 && t->sb % 8 == 0 && (!t->data || ((uintptr_t)t->data & 15) == 0); }
+
+extern "C" int coma_gate_eval_mfma_ok(const coma_tensor* g, const coma_tensor* x, int32_t F) {
+  if (!g || !x) return 0;
+  return g->dtype == COMA_BF16 && x->dtype == COMA_BF16 && t_same_grid(g, x) && g->C == x->C && x->C % 16 == 0 && x->C >= 16 &&
+         x->C <= 64 && F >= 1 && F <= 32 && gate_al16(g) && gate_al16(x) ? 1 : 0;
+}
+
+// one grid pass covers GATE_EVAL_MFMA_BLOCKS blocks x 4 waves x 32 voxels per sample (conv_mfma_pw_k's cap)
+#define GATE_EVAL_MFMA_BLOCKS 2048
+extern "C" int coma_gate_eval_mfma(const coma_tensor* g, const coma_tensor* x, const void* wg_folded, const void* wx_folded,
+                                   const float* shift, const float* w_psi, const float* psi_ab, const coma_tensor* psi,
+                                   const coma_tensor* att, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COMA_CHECK(g && x && att && g->data && x->data && att->data && wg_folded && wx_folded && shift && w_psi && psi_ab &&
+             (!psi || psi->data), "gate_eval_mfma: null argument");
+  COMA_CHECK(t_same_grid(x, att) && x->C == att->C && att->dtype == COMA_BF16 &&
+             (!psi || (t_same_grid(x, psi) && psi->C == 1 && psi->dtype == COMA_BF16)), "gate_eval_mfma: shape/dtype mismatch");
+  COMA_CHECK(coma_gate_eval_mfma_ok(g, x, 32) && gate_al16(att), "gate_eval_mfma: unsupported problem (ask coma_gate_eval_mfma_ok)");
+  COMA_CHECK((((uintptr_t)wg_folded | (uintptr_t)wx_folded) & 15) == 0, "gate_eval_mfma: folded weights must be 16-byte aligned");
+  GateEvalP p{};
+  gate_eval_common(p, x, psi, att);
+  p.g1 = g->data; p.ldg = g->ld; p.sbg = g->sb;
+  p.F = 32; p.wg = wg_folded; p.wx = wx_folded; p.sh = shift; p.w = w_psi; p.ab = psi_ab;
+  int64_t nb = ((p.V + 31) / 32 + 3) / 4;
+  if (nb > GATE_EVAL_MFMA_BLOCKS) nb = GATE_EVAL_MFMA_BLOCKS;
+  dim3 grid((unsigned)nb, (unsigned)x->B);
+  const int ks = x->C / 16;
+  if (ks == 1) hipLaunchKernelGGL((gate_eval_mfma_k<1>), grid, dim3(256), 0, s, p);
+  else if (ks == 2) hipLaunchKernelGGL((gate_eval_mfma_k<2>), grid, dim3(256), 0, s, p);
+  else if (ks == 3) hipLaunchKernelGGL((gate_eval_mfma_k<3>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((gate_eval_mfma_k<4>), grid, dim3(256), 0, s, p);
   COMA_LAUNCH_CHECK();
   return 0;
 }

@@ -43,6 +43,11 @@ class Config:
         import os
         self.fused_gate = os.environ.get("COMA_FUSED_GATE", "1") not in ("0", "")
         self.grad_forks = os.environ.get("COMA_GRAD_FORKS", "1") not in ("0", "")
+        # inference (inference.Predictor sets both for the duration of its own forwards only): eval-mode attention gates
+        # that carry a fold run as one fused launch, and eval BatchNorms found in `eval_stats` ({module: (mean, rstd)})
+        # take their folded statistics instead of deriving rstd from running_var in every forward
+        self.eval_fused = False
+        self.eval_stats = None
 
     def begin_forward(self):
         self.nbt_pending = []
@@ -105,6 +110,9 @@ def _norm_params(cfg, bn, training):
 def norm_act(cfg, x, bn, mode, act, slope, training, out=None, pre=None):
     """`pre`: the statistics record the convolution that wrote `x` produced (ops.ConvLayer with norm=mode)."""
     gamma, beta, rmean, rvar, momentum, eps = _norm_params(cfg, bn, training)
+    if cfg.eval_fused and bn is not None and not training and cfg.eval_stats is not None:
+        return ops.NormAct.apply(x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, training,
+                                 Out(out) if out is not None else None, pre, cfg.eval_stats.get(bn))
     return ops.NormAct.apply(x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, training,
                              Out(out) if out is not None else None, pre)
 
@@ -129,15 +137,16 @@ def conv_then_bn(cfg, x, cv, bn, act, training, out=None):
     return norm_act(cfg, y, bn, L.NORM_BATCH, act, None, True, out, pre=sums)
 
 
-def conv_plain(cfg, x, conv: nn.Module, ksize, stride, transposed, out=None, norm=None):
-    """nn.Conv3d / nn.ConvTranspose3d semantics with shared weights."""
+def conv_plain(cfg, x, conv: nn.Module, ksize, stride, transposed, out=None, norm=None, with_bias=True):
+    """nn.Conv3d / nn.ConvTranspose3d semantics with shared weights.  with_bias=False: the bare product (the caller has
+    folded the bias elsewhere: the eval-mode attention gate)."""
     n_out = conv.weight.shape[1] if transposed else conv.weight.shape[0]
     a_f, a_d = ops.pick_algo(x.shape, x.dtype, n_out, ksize, stride, transposed, False, x.device, cfg.conv_algo)
     need_dx = x.requires_grad
     fdt, ddt = _wdtype(a_f), (_wdtype(a_d) if need_dx else None)
     pre = ops.PrepAhead.take(conv.weight, transposed, fdt, ddt)        # prepared at the start of this forward?
     ops.PrepAhead.note(conv.weight, None, None, transposed, fdt, ddt)
-    return ops.ConvLayer.apply(x, conv.weight, None, conv.bias, ksize, stride, transposed, cfg.conv_algo,
+    return ops.ConvLayer.apply(x, conv.weight, None, conv.bias if with_bias else None, ksize, stride, transposed, cfg.conv_algo,
                                Out(out) if out is not None else None, norm, fdt, ddt,
                                cfg.zero_bias_grad_under_norm, pre[2:] if pre is not None else None)
 

@@ -964,7 +964,9 @@ class NormAct(Function):
     derive mean / rstd from the record themselves; the forward apply also moves BatchNorm's running statistics."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, training, out, pre=None):
+    def forward(ctx, x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, training, out, pre=None, eval_mr=None):
+        """eval_mr: eval-mode BatchNorm's (mean, rstd) fp32 (1, C) tensors when the caller keeps them folded (inference.Predictor)
+        instead of deriving them from the running statistics in every forward."""
         ctx.params = (gamma, beta, slope)
         dev = x.device
         B, C = x.shape[0], x.shape[4]
@@ -978,6 +980,8 @@ class NormAct(Function):
         elif use_batch_stats:
             sums = stat_record(G, C, 2, dev)
             check(lib.coma_norm_stats(cx, mode, ptr(sums), s), "coma_norm_stats")
+        elif eval_mr is not None:
+            mean, rstd = eval_mr
         else:
             mean = rmean.reshape(1, C).float().contiguous()
             rstd = torch.rsqrt(rvar.reshape(1, C).float() + eps).contiguous()
@@ -1015,7 +1019,7 @@ class NormAct(Function):
                                       "coma_norm_act_bwd"),
                         name="norm_bwd_partial_k + norm_act_bwd_apply_k<%s>" % ("__bf16" if x.dtype == torch.bfloat16 else "float"))
         return (dx, None if sinks[0] is not None else dgamma, None if sinks[1] is not None else dbeta,
-                None if sinks[2] is not None else dslope, None, None, None, None, None, None, None, None, None)
+                None if sinks[2] is not None else dslope, None, None, None, None, None, None, None, None, None, None)
 
 
 # --------------------------------------------------------------------------------------
@@ -1133,6 +1137,39 @@ class GateFused(Function):
         w_shape = ctx.params[4].shape
         return (None if shared else dx, dg1, dx1, None, None, ret(0, dgg), ret(1, dbg), ret(2, dgx), ret(3, dbx),
                 ret(4, dw.view(w_shape)), db_psi, ret(5, dgp), ret(6, dbp), None, None, None, None)
+
+
+def gate_eval_mfma_ok(g, x, f_int):
+    """Does the one-launch MFMA form of the eval gate take these tensors (csrc/gate.hip: gate_eval_mfma_k)?"""
+    return bool(lib.coma_gate_eval_mfma_ok(ct(g), ct(x), int(f_int)))
+
+
+def gate_eval_mfma(g, x, fold, out=None, want_psi=False):
+    """The whole eval-mode gate, W_g / W_x convolutions included, in one launch.  fold: inference.fold_gate's tensors.
+    Returns (att, psi or None).  No autograd: inference only."""
+    att = out if out is not None else _new(x.shape, x.dtype, x.device)
+    psi = _new(tuple(x.shape[:4]) + (1,), x.dtype, x.device) if want_psi else None
+    tb = float(x.numel() * x.element_size())              # algorithmic bytes: g and x read, att written (+ psi)
+    KernelTimer.run("gate_eval", "hbm", (0.0, 3.0 * tb),
+                    lambda: check(lib.coma_gate_eval_mfma(ct(g), ct(x), ptr(fold["wg"]), ptr(fold["wx"]), ptr(fold["shift32"]),
+                                                          ptr(fold["w_psi32"]), ptr(fold["psi_ab"]), ct(psi) if psi is not None else None,
+                                                          ct(att), L.stream()), "coma_gate_eval_mfma"),
+                    tag=tuple(x.shape), name="gate_eval_mfma_k<%d>" % (x.shape[4] // 16))
+    return att, psi
+
+
+def gate_eval_fwd(x, g1raw, x1raw, fold, out=None, want_psi=False):
+    """The eval-mode gate behind its (bias-free) W_g / W_x products in one launch (gate_eval_fwd_k)."""
+    att = out if out is not None else _new(x.shape, x.dtype, x.device)
+    psi = _new(tuple(x.shape[:4]) + (1,), x.dtype, x.device) if want_psi else None
+    tb = float(x.numel() * x.element_size())
+    KernelTimer.run("gate_eval", "hbm", (0.0, 2.0 * tb + 2.0 * g1raw.numel() * g1raw.element_size()),
+                    lambda: check(lib.coma_gate_eval_fwd(ct(x), ct(g1raw), ct(x1raw), ptr(fold["scale_g"]), ptr(fold["scale_x"]),
+                                                         ptr(fold["shift"]), ptr(fold["w_psi"]), ptr(fold["psi_ab"]),
+                                                         ct(psi) if psi is not None else None, ct(att), L.stream()),
+                                  "coma_gate_eval_fwd"),
+                    tag=tuple(x.shape), name="gate_eval_fwd_k<%s>" % ("__bf16" if x.dtype == torch.bfloat16 else "float"))
+    return att, psi
 
 
 class JoinSlices(Function):

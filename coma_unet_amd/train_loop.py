@@ -340,7 +340,7 @@ def _save_corr_matrices(corr, save_path, prefix):
 
 
 def contrastive_test(model, test_loader, roi_indices, roi_weights, save_path="", cuda_id=0, pred_sample_file="",
-                     with_train_loader=False, **kwargs):
+                     with_train_loader=False, predictor=None, **kwargs):
     """attn_unet_data_parallel.py:1129.  Returns (general, pos, neg) [+ embeddings when model.embeddings_out], each a
     tuple (mae, mape, rse, rrmse, ssim, roi_maes, roi_mapes, roi_rses, roi_wrrmses, roi_correlations); `general` carries an
     11th entry, the (never updated upstream, :1184-1185,1358) voxel-MAPE volume.
@@ -372,8 +372,12 @@ def contrastive_test(model, test_loader, roi_indices, roi_weights, save_path="",
         mri, tau, roi, abeta, covars, tau_path = _unpack(values)
         mri, tau, roi, covars = (_dev(t, device) for t in (mri, tau, roi, covars))
         priors = [lookup[get_id(p)] for p in tau_path]
-        with torch.no_grad():
-            pred = model(mri, covars, roi_pred_dicts=priors, sample_roi_mask=roi)                         # :1209
+        if predictor is not None and predictor.fits(mri):
+            # the folded, graph-replayed forward (inference.Predictor); its output buffer is rewritten by the next call
+            pred = predictor({"mri": mri, "covars": covars, "roi": roi, "roi_pred_dicts": priors}).clone()
+        else:             # (also the last, smaller batch of a loader: the predictor's buffers have one fixed shape)
+            with torch.no_grad():
+                pred = model(mri, covars, roi_pred_dicts=priors, sample_roi_mask=roi)                     # :1209
         if model.embeddings_out:
             pred, projected, _final, inter = pred
             for i in range(len(projected)):

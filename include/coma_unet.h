@@ -237,6 +237,27 @@ int coma_gate_mid_bwd(const coma_tensor* dz, const coma_tensor* psi_raw, const c
                       float* dgamma_g, float* dbeta_g, float* dgamma_x, float* dbeta_x, float* dw_psi,
                       float* dgamma_psi, float* dbeta_psi, void* stream);
 
+/* ---- the attention gate with every BatchNorm in EVAL mode: each is a known affine map, so the gate is one pass
+ *      att = x * psi,   psi = sigmoid(a_p * (w_psi . relu(scale_g * g1raw + scale_x * x1raw + shift)) + b_p)
+ * The caller folds the running statistics ONCE into fp32 device tables: scale_g[F] = gamma_g * rstd_g, scale_x[F],
+ * shift[F] (both betas, both means, both convolution biases when g1raw / x1raw are bias-free products), w_psi[F] and
+ * psi_ab[2] = {a_p, b_p} = {gamma_p rstd_p, a_p b_psi + beta_p - a_p mean_p}.  psi ([B][V][1]) may be NULL; att may be a
+ * channel slice of a wider buffer.  Nothing is saved: there is no backward.                                          */
+/* behind the W_g / W_x convolutions: g1raw, x1raw have F channels; x, att have C.  Any dtype, F and C the training gate
+ * kernels take (max(C, F) / vector width a power of two <= 64, F <= 512).                                          */
+int coma_gate_eval_fwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw, const float* scale_g,
+                       const float* scale_x, const float* shift, const float* w_psi, const float* psi_ab,
+                       const coma_tensor* psi, const coma_tensor* att, void* stream);
+/* The whole gate INCLUDING both 1x1x1 convolutions in one launch (bf16 MFMA, no intermediate ever in memory):
+ * wg_folded / wx_folded are bf16 [32][C] = diag(scale_g) W_g, diag(scale_x) W_x with ZERO rows beyond F, and shift / w_psi
+ * here have 32 entries, zero beyond F (shift carries the biases): the padded rows contribute exactly nothing.
+ * coma_gate_eval_mfma_ok answers 1 where this form runs: bf16 g and x on one grid with C % 16 == 0, 16 <= C <= 64,
+ * 1 <= F <= 32, 16-byte aligned data and pitches; 0 otherwise (then use coma_gate_eval_fwd behind the convolutions). */
+int coma_gate_eval_mfma_ok(const coma_tensor* g, const coma_tensor* x, int32_t F);
+int coma_gate_eval_mfma(const coma_tensor* g, const coma_tensor* x, const void* wg_folded, const void* wx_folded,
+                        const float* shift, const float* w_psi, const float* psi_ab, const coma_tensor* psi,
+                        const coma_tensor* att, void* stream);
+
 /* ---- generic strided element-wise helpers ---- */
 /* dst = a (+ b).  b may be NULL.  a/b with B == 1 broadcast over dst's batch. */
 int coma_add(const coma_tensor* a, const coma_tensor* b, const coma_tensor* dst, void* stream);
