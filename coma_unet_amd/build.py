@@ -6,7 +6,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcoma_unet.so")
-SOURCES = ["api.hip", "conv_direct.hip", "conv_point1.hip", "conv_mfma.hip", "conv_split.hip", "norm.hip", "gate.hip", "elementwise.hip", "weights.hip", "metrics.hip", "comm.hip"]
+# (the two slowest to compile first)
+SOURCES = ["conv_mfma.hip", "conv_wgrad.hip", "api.hip", "conv_direct.hip", "conv_point1.hip", "conv_split.hip", "norm.hip", "gate.hip",
+           "elementwise.hip", "weights.hip", "metrics.hip", "comm.hip"]
+MAX_PROCS = 16      # compiler processes at a time
 
 
 def _stale(obj, deps):
@@ -29,6 +32,8 @@ def build(force=False, verbose=True):
             cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", sp, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
+            if len(procs) >= MAX_PROCS:      # (wait for the one started MAX_PROCS launches ago: then at most MAX_PROCS - 1 others can still be running)
+                procs[len(procs) - MAX_PROCS][1].wait()
             procs.append((src, subprocess.Popen(cmd)))
     failed = [s for s, p in procs if p.wait() != 0]
     if failed:

@@ -1,5 +1,5 @@
 // C-ABI entry points that dispatch between kernel families, plus error reporting.
-#include "common.h"
+#include "conv_mfma.h"
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -36,18 +36,7 @@ int conv_point1_fwd(const coma_conv_desc* d, const coma_tensor* x, const float* 
 int conv_point1_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed);
 // norm.hip
 int colsum(const coma_tensor* x, int per_sample, float* out, void* ws, size_t ws_bytes, hipStream_t s);
-// conv_mfma.hip
-bool conv_mfma_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-bool conv_f32mfma_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-int conv_mfma_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias,
-                  const coma_tensor* y, hipStream_t s, double2* stats = nullptr, int stats_inst = 0,
-                  int* stats_chunks = nullptr, void* ws = nullptr, size_t ws_bytes = 0, int ws_zeroed = 0, int accum = 0);
-bool conv_mfma_accumulate_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-size_t conv_mfma_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-bool conv_mfma_wgrad_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
-size_t conv_mfma_wgrad_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
-int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
-                    size_t ws_bytes, hipStream_t s, int zeroed);
+// conv_mfma.hip: conv_mfma.h
 // conv_split.hip (algo 4: fp32 tensors, two-term bf16 split on the bf16 matrix pipe)
 bool conv_split_fwd_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 int conv_split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,

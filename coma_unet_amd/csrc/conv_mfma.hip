@@ -9,8 +9,9 @@
 //
 // Replaces the cuDNN dispatches behind nn.Conv3d / nn.ConvTranspose3d forward and data-gradient
 // in the reference model (attn_unet_data_parallel.py; MONAI Convolution / CondConv call sites).
-#include "common.h"
-#include "conv_tiles.h"   // bf16x8_t / f32x16_t, stat_add, xcd_remap, tile_coords
+// Further down: the stride-1 and voxels-along-K weight-gradient kernels and the dispatch of all of them; the two
+// weight-gradient kernels on 32 x 32 tiles chosen by wgrad_plan (conv_mfma_wgrad_k, conv_f32_wgrad_k) are in conv_wgrad.hip.
+#include "conv_mfma.h"   // load8 / mask8, aligned16, s4_t, the replica constants; conv_tiles.h: tile_run, set_max_lds, stat_add, ...
 #include <type_traits>
 
 // ---- element type of the activations / kernel-layout weights: bf16 (v_mfma_f32_32x32x16_bf16) or fp32
@@ -260,36 +261,6 @@ __global__ __launch_bounds__(256) void gather_finalize_k(const float* __restrict
     T* dst = y + (long)b * sby + v * ldy + n;
     *dst = static_cast<T>(part[(long)b * part_sb + e] + (bias ? bias[b * bsb + n] : 0.f) + (accum ? static_cast<float>(*dst) : 0.f));
   }
-}
-
-// 8 channels starting at `ptr`, of which `nvalid` exist; `vec` = 16-byte access is legal here: the base is 16-byte
-// aligned and the voxel pitch is a multiple of 8 channels, so the 8-channel piece lies inside the voxel's row even when
-// fewer than 8 of its channels belong to this tensor (a channel slice of a wider, padded buffer) -- those are masked off.
-__device__ __forceinline__ uint4 load8(const bf16_t* ptr, int nvalid, bool vec) {
-  if (vec) {
-    uint4 v = *reinterpret_cast<const uint4*>(ptr);
-    if (nvalid < 8) {
-      auto m = [&](int j) -> unsigned { const int k = nvalid - 2 * j; return k >= 2 ? 0xffffffffu : (k == 1 ? 0xffffu : 0u); };
-      v.x &= m(0); v.y &= m(1); v.z &= m(2); v.w &= m(3);
-    }
-    return v;
-  }
-  unsigned short e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) e[j] = j < nvalid ? reinterpret_cast<const unsigned short*>(ptr)[j] : (unsigned short)0;
-  return make_uint4(e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16), e[4] | ((unsigned)e[5] << 16),
-                    e[6] | ((unsigned)e[7] << 16));
-}
-
-// The same piece WITHOUT the mask when the vector access is legal: a prefetch must not consume its data (the mask would
-// put an s_waitcnt vmcnt(0) behind every load and serialise a tile's 13 loads); apply mask8() when the piece is stored.
-__device__ __forceinline__ uint4 load8_raw(const bf16_t* ptr, int nvalid, bool vec) {
-  if (vec) return *reinterpret_cast<const uint4*>(ptr);
-  return load8(ptr, nvalid, false);
-}
-__device__ __forceinline__ uint4 mask8(int nvalid) {
-  auto m = [&](int j) -> unsigned { const int k = nvalid - 2 * j; return k >= 2 ? 0xffffffffu : (k == 1 ? 0xffffu : 0u); };
-  return make_uint4(m(0), m(1), m(2), m(3));
 }
 
 // =====================================================================================
@@ -1887,10 +1858,13 @@ __global__ __launch_bounds__(256, 2) void conv_thin16f_k(Thin16FP p) {
   }
 }
 
-static bool aligned16(const void* p);
-static bool thin16f_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+// COMA_THIN16F=0: the fp32 few-channel layers on the generic fp32 kernels (forward and weight gradient alike)
+static bool thin16f_on() {
   static const bool on = []{ const char* e = getenv("COMA_THIN16F"); return !(e && e[0] == '0'); }();
-  return on && d->ksize == 3 && d->stride == 1 && x->dtype == COMA_F32 && y->dtype == COMA_F32 && x->W >= 32 && x->C <= 16 &&
+  return on;
+}
+static bool thin16f_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return thin16f_on() && d->ksize == 3 && d->stride == 1 && x->dtype == COMA_F32 && y->dtype == COMA_F32 && x->W >= 32 && x->C <= 16 &&
          y->C <= (x->C > 8 ? 16 : 32) && x->ld % 4 == 0 && x->sb % 4 == 0 && (!x->data || aligned16(x->data)) &&
          (unsigned long long)t_vox(x) * x->ld * 4 < 0x7fff0000ull && (long)t_vox(y) * y->ld < (1L << 31);
 }
@@ -1905,32 +1879,20 @@ static int conv_thin16f(const coma_conv_desc* d, const coma_tensor* x, const voi
   q.flip = d->form == 1;
   q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
   q.st16 = y->ld % 4 == 0 && y->sb % 4 == 0 && (((uintptr_t)y->data) & 15) == 0;
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
-  int gx = 512 / x->B;                                 // two blocks per CU, one round (a tile is 16x the bf16 MFMA time)
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, x->B);      // two blocks per CU, one round (a tile is 16x the bf16 MFMA time)
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   q.stats = nullptr; q.stats_inst = stats_inst;
   if (stats) { q.stats = stats; *stats_chunks = 1; }
-  const dim3 grid((unsigned)gx, 1, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
   const bool c16 = q.C > 8, n32 = q.N > 16;
   const int cp = c16 ? 16 : q.C > 4 ? 8 : 4, wrow = n32 ? 32 : 16;      // (C <= 4: one MFMA per tap)
   const size_t lds = (size_t)34 * 6 * 4 * cp * 4 + (size_t)27 * wrow * cp * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_k<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_k<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_k<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_k<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_k<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr = true;
-  }
   coma_set_kernel_tag("conv_thin16f_k<%d, %d>", cp, n32 ? 2 : 1);
-  if (c16) hipLaunchKernelGGL((conv_thin16f_k<16, 1>), grid, dim3(256), lds, s, q);
-  else if (cp == 8) { if (n32) hipLaunchKernelGGL((conv_thin16f_k<8, 2>), grid, dim3(256), lds, s, q); else hipLaunchKernelGGL((conv_thin16f_k<8, 1>), grid, dim3(256), lds, s, q); }
-  else { if (n32) hipLaunchKernelGGL((conv_thin16f_k<4, 2>), grid, dim3(256), lds, s, q); else hipLaunchKernelGGL((conv_thin16f_k<4, 1>), grid, dim3(256), lds, s, q); }
+#define THIN16F(CP_, NB_) do { set_max_lds<conv_thin16f_k<CP_, NB_>, 80>(); hipLaunchKernelGGL((conv_thin16f_k<CP_, NB_>), grid, dim3(256), lds, s, q); } while (0)
+  if (c16) THIN16F(16, 1);
+  else if (cp == 8) { if (n32) THIN16F(8, 2); else THIN16F(8, 1); }
+  else { if (n32) THIN16F(4, 2); else THIN16F(4, 1); }
+#undef THIN16F
   COMA_LAUNCH_CHECK();
   return 0;
 }
@@ -2113,8 +2075,6 @@ __global__ __launch_bounds__(256) void conv_mfma_pw_k(PwP p) {
     }
   }
 }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static bool halo_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   // stride-1 3x3x3 (either gather form); any channel counts; rows wide enough to fill 32-voxel M-tiles
@@ -2483,30 +2443,17 @@ static int conv_mfma_tconv(const coma_conv_desc* d, const coma_tensor* x, const 
   q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * sizeof(T));
   q.wbytes = (unsigned)(27ull * y->C * x->C * sizeof(T));
   q.accum = accum;
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   const int nblk_n = y->C / 32;
-  int gx = 512 / (nblk_n * x->B);                      // one block per CU, about two rounds
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, nblk_n * x->B);      // one block per CU, about two rounds
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   q.stats = nullptr; q.stats_inst = stats_inst;
   static const bool fuse_stats = getenv("COMA_TCONV_NO_STATS") == nullptr;      // (A/B: statistics as a separate pass)
   if (stats && !accum && fuse_stats) { q.stats = stats; *stats_chunks = 1; }
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma_tconv_k<bf16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_tconv_k<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_tconv_k<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_tconv_k<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
   const size_t lds = (size_t)(33 * 5 * 3 + 14 * 32) * 80;
   coma_set_kernel_tag("conv_mfma_tconv_k<%s, %d>", sizeof(T) == 2 ? "__bf16" : "float", q.stats ? 1 : 0);
-  const dim3 grid((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B);
-  if (q.stats) hipLaunchKernelGGL((conv_mfma_tconv_k<T, true>), grid, dim3(256), lds, s, q);
-  else hipLaunchKernelGGL((conv_mfma_tconv_k<T, false>), grid, dim3(256), lds, s, q);
+  const dim3 grid((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B);
+  if (q.stats) { set_max_lds<conv_mfma_tconv_k<T, true>>(); hipLaunchKernelGGL((conv_mfma_tconv_k<T, true>), grid, dim3(256), lds, s, q); }
+  else { set_max_lds<conv_mfma_tconv_k<T, false>>(); hipLaunchKernelGGL((conv_mfma_tconv_k<T, false>), grid, dim3(256), lds, s, q); }
   COMA_LAUNCH_CHECK();
   return 0;
 }
@@ -2563,18 +2510,28 @@ static int gather_ksplit(long blocks, int nsteps, bool f32) {
   return ks < 2 ? 1 : (int)ks;
 }
 
+// grid of a gather launch (BN output channels and 128 / 256 voxels of the Mtot-voxel M-grid per block; mode 1: one parity
+// class of 8 taps per blockIdx.y slice, which bounds the split) and its split-K factor
+struct GatherGrid { long gx, gy; int ksplit; };
+static GatherGrid gather_grid(int BN, int mode, long Mtot, int N, int B, int taps, int C, bool f32) {
+  const int BM = BN == 128 ? 128 : 256, LCK = f32 ? 4 : 5;
+  GatherGrid g;
+  g.gx = (Mtot + BM - 1) / BM; g.gy = (long)(N / BN) * (mode == 1 ? 8 : 1);
+  g.ksplit = gather_ksplit(g.gx * g.gy * B, (mode == 1 ? 1 : taps) * (C >> LCK), f32);
+  return g;
+}
+
 template <int BN, typename T>
 static int launch_gather(const GatherP& p0, int mode, int B, hipStream_t s, void* ws, size_t ws_bytes, int ws_zeroed,
                          double2* stats, int stats_inst, int* stats_chunks) {
   GatherP p = p0;
   constexpr int BM = (BN == 128) ? 128 : 256;
   constexpr int LCK = elem<T>::EPB == 8 ? 5 : 4;
-  const long Mtot = (long)p.Mz * p.My * p.Mx;
   const size_t lds = (size_t)2 * (BM + BN) * 64 + BM * 4;
-  const unsigned gx = (unsigned)((Mtot + BM - 1) / BM), gy = (unsigned)(p.N / BN) * (mode == 1 ? 8 : 1);
+  const GatherGrid g = gather_grid(BN, mode, (long)p.Mz * p.My * p.Mx, p.N, B, p.k * p.k * p.k, p.C, LCK == 4);
+  const unsigned gx = (unsigned)g.gx, gy = (unsigned)g.gy;
   const long Vout = (long)p.Do * p.Ho * p.Wo;
-  const int ntaps_max = mode == 1 ? 8 : p.k * p.k * p.k;      // (mode 1: the 8-tap parity class bounds the split)
-  p.ksplit = gather_ksplit((long)gx * gy * B, (mode == 1 ? 1 : ntaps_max) * (p.C >> LCK), LCK == 4);
+  p.ksplit = g.ksplit;
   p.part = nullptr; p.part_sb = 0;
   if (p.ksplit > 1 && ws && ws_bytes >= sizeof(float) * (size_t)B * Vout * p.N) {
     p.part = (float*)ws; p.part_sb = Vout * p.N;
@@ -2604,8 +2561,7 @@ static int launch_halo(const HaloP& p0, int B, hipStream_t s) {
   constexpr int HV = (TX + 2) * (TY + 2) * (TZ + 2);
   p.ntx = (p.W + TX - 1) / TX; p.nty = (p.H + TY - 1) / TY; p.ntz = (p.D + TZ - 1) / TZ;
   const size_t lds = (size_t)(HV + 9 * 32) * CK * sizeof(T);
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)conv_mfma_halo_k<CK, LX, VEC, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr = true; }
+  set_max_lds<conv_mfma_halo_k<CK, LX, VEC, T>, 96>();
   dim3 grid((unsigned)(p.ntx * p.nty * ((p.ntz + 7) / 8) * 8), (unsigned)((p.N + 31) / 32), (unsigned)B);
   coma_set_kernel_tag("conv_mfma_halo_k<%d, %d, %d, %s>", CK, LX, VEC, sizeof(T) == 4 ? "float" : "__bf16");
   hipLaunchKernelGGL((conv_mfma_halo_k<CK, LX, VEC, T>), grid, dim3(256), lds, s, p);
@@ -2614,10 +2570,13 @@ static int launch_halo(const HaloP& p0, int B, hipStream_t s) {
 }
 
 // bytes of scratch conv_mfma_duo_k wants for a fragment-ordered copy of the weights (C >= 64 stride-1 3^3 bf16 layers), else 0
-static bool aligned16(const void* p);
+// COMA_NO_DUO=1: conv_mfma_halo2_k everywhere (0); COMA_DUO_C32_ONLY=1: the C == 32 layers only (1); default: all (2)
+static int duo_mode() {
+  static const int mode = getenv("COMA_NO_DUO") != nullptr ? 0 : getenv("COMA_DUO_C32_ONLY") != nullptr ? 1 : 2;
+  return mode;
+}
 static size_t duo_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
-  static const bool on = getenv("COMA_DUO_C32_ONLY") == nullptr && getenv("COMA_NO_DUO") == nullptr;
-  if (!on || x->dtype != COMA_BF16 || d->ksize != 3 || d->stride != 1 || x->W < 16) return 0;
+  if (duo_mode() < 2 || x->dtype != COMA_BF16 || d->ksize != 3 || d->stride != 1 || x->W < 16) return 0;
   if (x->C < 64 || x->C % 16 || y->C % 32) return 0;
   return (size_t)(d->per_sample_w ? x->B : 1) * 27 * y->C * x->C * 2;
 }
@@ -2652,16 +2611,11 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
       q.y = (bf16_t*)p.y; q.ldy = p.ldy; q.sby = p.sby; q.N = p.N; q.w = (const bf16_t*)p.w; q.wsb = p.wsb; q.bias = p.bias; q.bsb = p.bsb;
       q.flip = p.flip; q.xbytes = (unsigned)xb_;
       q.st8 = y->ld % 4 == 0 && y->sb % 4 == 0 && (((uintptr_t)y->data) & 7) == 0;
-      q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-      q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
-      int gx = 1024 / x->B;                              // >= 2 blocks per CU
-      if (gx < 1) gx = 1;
-      if (gx > q.ids_total) gx = q.ids_total;
-      q.ids_per_block = (q.ids_total + gx - 1) / gx;
-      gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+      const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 1024, x->B);      // >= 2 blocks per CU
+      q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
       q.stats = nullptr; q.stats_inst = stats_inst;
       if (stats) { q.stats = stats; *stats_chunks = 1; }
-      dim3 grid((unsigned)gx, 1, (unsigned)x->B);
+      dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
       const bool c16 = q.C > 8, n32 = q.N > 16;
       size_t lds = (size_t)34 * 6 * 4 * (c16 ? 32 : 16);
       if (lds < (size_t)27 * q.N * q.C * 2) lds = (size_t)27 * q.N * q.C * 2;     // the weights are staged there first (<= 13.8 KB)
@@ -2686,16 +2640,11 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
     q.st8 = y->ld % 4 == 0 && y->sb % 4 == 0 && (((uintptr_t)y->data) & 7) == 0;
     q.st16 = y->ld % EPB == 0 && y->sb % EPB == 0 && (((uintptr_t)y->data) & 15) == 0;
     const int txv = lx == 5 ? 32 : 16, tyv = lx == 5 ? 4 : 8;      // tile: 2 x 4 x 32 voxels, or 2 x 8 x 16 on the 16-wide grids
-    q.ntx = (q.W + txv - 1) / txv; q.nty = (q.H + tyv - 1) / tyv; q.ntz = (q.D + 1) / 2;
-    q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
     const int nblk_n = (q.N + 31) / 32;
-    int gx = (thin ? 1024 : 512) / (nblk_n * x->B);   // thin: 2 blocks per CU, thick: 1
-    if (F32) gx = 256 / (nblk_n * x->B);               // fp32 tiles are 16x longer: one round of one block per CU balances best
-    if (gx < 1) gx = 1;
-    if (gx > q.ids_total) gx = q.ids_total;
-    q.ids_per_block = (q.ids_total + gx - 1) / gx;
-    gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
-    dim3 grid((unsigned)gx, (unsigned)nblk_n, (unsigned)x->B);
+    // thin: 2 blocks per CU, thick: 1; fp32 tiles are 16x longer: one round of one block per CU balances best
+    const TileRun r = tile_run(q.D, q.H, q.W, txv, tyv, 2, F32 ? 256 : thin ? 1024 : 512, nblk_n * x->B);
+    q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
+    dim3 grid((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B);
     if (stats) { q.stats = stats; *stats_chunks = 1; }
     if constexpr (!F32) {
       // two 4-wave groups per CU alternating matrix and staging phases (conv_mfma_duo_k): full 32-channel output tiles with
@@ -2706,7 +2655,7 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
       // (duo_relayout_k into the caller's scratch, coma_conv_fwd_ws_bytes): 64 -> 32 696 / 691 and 665 / 689 (data gradient),
       // 64 -> 64 at 64^3 129 / 144 and 134 / 150, 128 -> 64 270 / 273 and 277 / 297, 256 -> 128 at 32^3 117 / 125 and 126 / 134;
       // step 18.09 -> 17.99 ms.  COMA_NO_DUO=1: conv_mfma_halo2_k everywhere; COMA_DUO_C32_ONLY=1: the C == 32 layers only.
-      static const bool no_duo = getenv("COMA_NO_DUO") != nullptr, duo_all = getenv("COMA_DUO_C32_ONLY") == nullptr;
+      const bool no_duo = duo_mode() == 0, duo_all = duo_mode() == 2;
       q.wfrag = nullptr; q.wfrag_sb = 0;
       const size_t frag_bytes = duo_frag_bytes(d, x, y);      // C >= 64: scratch for the fragment-ordered copy of the weights
       const bool wide_ok = duo_all && q.C > 32 && frag_bytes > 0 && ws && ws_bytes >= frag_bytes && aligned16(ws);
@@ -2718,31 +2667,22 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
           COMA_LAUNCH_CHECK();
           q.wfrag = ws; q.wfrag_sb = d->per_sample_w ? 27L * q.N * q.C : 0;
         }
-        int g2 = 256 / (nblk_n * x->B);                   // one 512-thread block per CU, once
-        if (g2 < 1) g2 = 1;
-        if (g2 > q.ids_total) g2 = q.ids_total;
-        q.ids_per_block = (q.ids_total + g2 - 1) / g2;
-        g2 = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
-        const dim3 grid2((unsigned)g2, (unsigned)nblk_n, (unsigned)x->B);
+        const TileRun r2 = tile_run(q.D, q.H, q.W, txv, tyv, 2, 256, nblk_n * x->B);      // one 512-thread block per CU, once
+        q.ids_per_block = r2.ids_per_block;
+        const dim3 grid2((unsigned)r2.gx, (unsigned)nblk_n, (unsigned)x->B);
         if (stats) { q.stats = stats; *stats_chunks = 1; }
         const size_t lds2 = (size_t)2 * 34 * 6 * 4 * 48 + (size_t)2 * 27 * 64 * 16 + 128;
-        static bool attr2 = false;
-        if (!attr2) {
-          (void)hipFuncSetAttribute((const void*)conv_mfma_duo_k<0, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute((const void*)conv_mfma_duo_k<1, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute((const void*)conv_mfma_duo_k<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute((const void*)conv_mfma_duo_k<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          attr2 = true;
-        }
+#define DUO(ST_, LX_) do { set_max_lds<conv_mfma_duo_k<ST_, LX_>>(); hipLaunchKernelGGL((conv_mfma_duo_k<ST_, LX_>), grid2, dim3(512), lds2, s, q); } while (0)
         if (lx == 5) {
           coma_set_kernel_tag("conv_mfma_duo_k<%d, 5>", stats ? 1 : 0);
-          if (stats) hipLaunchKernelGGL((conv_mfma_duo_k<1, 5>), grid2, dim3(512), lds2, s, q);
-          else hipLaunchKernelGGL((conv_mfma_duo_k<0, 5>), grid2, dim3(512), lds2, s, q);
+          if (stats) DUO(1, 5);
+          else DUO(0, 5);
         } else {
           coma_set_kernel_tag("conv_mfma_duo_k<%d, 4>", stats ? 1 : 0);
-          if (stats) hipLaunchKernelGGL((conv_mfma_duo_k<1, 4>), grid2, dim3(512), lds2, s, q);
-          else hipLaunchKernelGGL((conv_mfma_duo_k<0, 4>), grid2, dim3(512), lds2, s, q);
+          if (stats) DUO(1, 4);
+          else DUO(0, 4);
         }
+#undef DUO
         COMA_LAUNCH_CHECK();
         return 0;
       }
@@ -2754,26 +2694,17 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
     // kz-plane streaming mode (RESIDENT = 0) it replaces left one plane of MFMAs (~0.5 us) to cover each weight fetch and
     // cost 14 barriers per tile: 64 -> 32 at 128^3 940 -> 832 us, 128 -> 64 at 64^3 384 -> 328 us, 256 -> 128 at 32^3 186 -> 157 us.
     const size_t lds = thin ? (size_t)(HV2 + 27 * 32) * 48 : (size_t)HV2 * 80 + (size_t)27 * 32 * 80;
-    static bool attr = false;
-    if (!attr) {
-      if constexpr (F32) {
-        (void)hipFuncSetAttribute((const void*)conv_mfma_halo2_k<2, 16, 1, 1, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      } else {
-        (void)hipFuncSetAttribute((const void*)conv_mfma_halo2_k<1, 32, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_mfma_halo2_k<2, 32, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_mfma_halo2_k<1, 16, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      }
-      attr = true;
-    }
     coma_set_kernel_tag(F32 ? "conv_mfma_halo2_k<2, 16, 1, 1, float>" : thin ? "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>"
                         : resident ? "conv_mfma_halo2_k<1, 32, 1, 1, __bf16>" : "conv_mfma_halo2_k<2, 32, 1, 1, __bf16>");
+#define HALO2(KB_, ...) do { set_max_lds<conv_mfma_halo2_k<__VA_ARGS__>, KB_>(); hipLaunchKernelGGL((conv_mfma_halo2_k<__VA_ARGS__>), grid, dim3(256), lds, s, q); } while (0)
     if constexpr (F32) {
-      hipLaunchKernelGGL((conv_mfma_halo2_k<2, 16, 1, 1, float>), grid, dim3(256), lds, s, q);
+      HALO2(160, 2, 16, 1, 1, float);
     } else {
-      if (thin) hipLaunchKernelGGL((conv_mfma_halo2_k<1, 16, 0, 2>), grid, dim3(256), lds, s, q);
-      else if (resident) hipLaunchKernelGGL((conv_mfma_halo2_k<1, 32, 1, 1>), grid, dim3(256), lds, s, q);
-      else hipLaunchKernelGGL((conv_mfma_halo2_k<2, 32, 1, 1>), grid, dim3(256), lds, s, q);
+      if (thin) HALO2(80, 1, 16, 0, 2);
+      else if (resident) HALO2(160, 1, 32, 1, 1);
+      else HALO2(160, 2, 32, 1, 1);
     }
+#undef HALO2
     COMA_LAUNCH_CHECK();
     return 0;
     }
@@ -2808,7 +2739,6 @@ bool conv_mfma_accumulate_ok(const coma_conv_desc* d, const coma_tensor* x, cons
   return conv_mfma_supported(d, x, y) && !halo_ok(d, x, y);
 }
 
-static int gather_ksplit(long blocks, int nsteps, bool f32);
 size_t conv_mfma_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   if (x->dtype == COMA_F32) { if (thin16f_ok(d, x, y) || f32_halo_ok(d, x, y)) return 0; }
   else if (halo_ok(d, x, y)) return duo_frag_bytes(d, x, y);
@@ -2816,15 +2746,12 @@ size_t conv_mfma_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, con
   if (tconv_ok(d, x, y)) return 0;
   const size_t bytes = sizeof(float) * (size_t)y->B * t_vox(y) * y->C;
   if (bytes > ((size_t)64 << 20)) return 0;
-  // only when launch_gather will really split the K loop (the same arithmetic as there): callers that hand out private
+  // only when launch_gather will really split the K loop (gather_grid): callers that hand out private
   // pre-zeroed scratch should not be asked for megabytes a launch never touches
-  const bool f32 = x->dtype == COMA_F32;
-  const int BN = y->C % 128 == 0 ? 128 : y->C % 64 == 0 ? 64 : 32, BM = BN == 128 ? 128 : 256, LCK = f32 ? 4 : 5;
+  const int BN = y->C % 128 == 0 ? 128 : y->C % 64 == 0 ? 64 : 32;
   const int mode = d->form == 1 && d->stride == 2;
   const long Mtot = mode ? (long)((y->D + 1) / 2) * ((y->H + 1) / 2) * ((y->W + 1) / 2) : (long)t_vox(y);
-  const long gx = (Mtot + BM - 1) / BM, gy = (long)(y->C / BN) * (mode ? 8 : 1);
-  const int taps = d->ksize * d->ksize * d->ksize;
-  return gather_ksplit(gx * gy * y->B, (mode ? 1 : taps) * (x->C >> LCK), f32) > 1 ? bytes : 0;
+  return gather_grid(BN, mode, Mtot, y->C, y->B, d->ksize * d->ksize * d->ksize, x->C, x->dtype == COMA_F32).ksplit > 1 ? bytes : 0;
 }
 
 int conv_mfma_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias,
@@ -2888,438 +2815,8 @@ int conv_mfma_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk,
   return launch_gather<32, bf16_t>(p, mode, x->B, s, ws, ws_bytes, ws_zeroed, stats, stats_inst, stats_chunks);
 }
 
-// =====================================================================================
-// Weight gradient on MFMA:  dwk[b][tap][n][c] = sum_m dy[.][n] * x[.][c]  over the voxels m of
-// the M-grid, one operand read densely and the other through a tap-shifted (strided) gather:
-//   FORM 0 (nn.Conv3d):          dense = dy[m],  gathered = x[m*stride - pad + tap]
-//   FORM 1 (nn.ConvTranspose3d): dense = x[m],   gathered = dy[m*2 - pad + tap]
-// A block stages one tile of dense voxels and the matching halo of the gathered tensor in LDS
-// as [voxel][channel] images, then every tap re-reads the SAME halo at its shifted address: the
-// 27-fold operand reuse happens in LDS, not in L2/HBM.  The GEMM reduction index is the voxel,
-// so both MFMA operands are read with ds_read_b64_tr_b16 (4 voxels x 16 channels per 16-lane
-// group, delivered channel-per-lane).  The 27 taps are dealt to the 4 waves (7,7,7,6); each wave
-// keeps its taps' 32x32 fp32 accumulators in registers across all tiles of the block
-// (weight-gradient-stationary) and merges them into dwk with fp32 atomics at the end.
-// =====================================================================================
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-
-struct WgradP2 {
-  const void* dyp; int ldn; long sbn;     // dy  (N channels)
-  const void* xp;  int ldc; long sbc;     // x   (C channels)
-  int N, C;
-  int Mz, My, Mx;      // dense grid
-  int Gz, Gy, Gx;      // gathered grid
-  int k, stride, pad;
-  int lx, ly, lz;      // log2 of the tile dims (tile = 2^lz x 2^ly x 2^lx dense voxels)
-  int hz, hy, hx;      // halo dims
-  int ntx, nty, ntz;   // tiles per dim
-  int tiles_total, tiles_per_block;
-  float* dwk; long wsb;
-  int cblocks;         // ceil(C / (32*TC))
-  int vec_n, vec_c;    // 16-byte loads legal on dy / x
-  unsigned m_hx, m_hxy; // magic multipliers: n / hx == umulhi(n, m_hx), n / (hx*hy) == umulhi(n, m_hxy)
-  int plain;           // every dwk element is produced by exactly one block: plain stores, no memset, no atomics
-  int cp, pg;          // fp32 kernel: gathered channels per tap in an MFMA tile (power of two <= 32), gathered LDS row pitch (bytes)
-  int nrep; long rep_stride;   // fp32 kernel, small outputs: blocks merge into one of nrep replicas (summed afterwards)
-};
-
-template <int TN, int TC, int FORM, int VEC>
-__global__ __launch_bounds__(256, 1) void conv_mfma_wgrad_k(WgradP2 p) {
-  constexpr int CDB = 32 * (FORM == 0 ? TN : TC);   // dense-side channels per block
-  constexpr int CGB = 32 * (FORM == 0 ? TC : TN);   // gathered-side channels per block
-  constexpr int PD = CDB * 2, PG = CGB * 2;         // LDS row pitches (bytes)
-  constexpr int MAXT = 7;                           // taps per wave
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int TM = 1 << (p.lx + p.ly + p.lz);
-  char* Dt = smem;
-  char* Gt = smem + TM * PD;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: tap lists live in SGPRs, tap tests are scalar branches
-  const int b = blockIdx.z;
-  const int nb = blockIdx.y / p.cblocks, cb = blockIdx.y % p.cblocks;
-  const int n0 = nb * 32 * TN, c0 = cb * 32 * TC;
-  const bf16_t* dyp16 = static_cast<const bf16_t*>(p.dyp);
-  const bf16_t* xp16 = static_cast<const bf16_t*>(p.xp);
-  const bf16_t* dense = (FORM == 0 ? dyp16 + (long)b * p.sbn + n0 : xp16 + (long)b * p.sbc + c0);
-  const bf16_t* gath = (FORM == 0 ? xp16 + (long)b * p.sbc + c0 : dyp16 + (long)b * p.sbn + n0);
-  const int ldd = FORM == 0 ? p.ldn : p.ldc, ldg = FORM == 0 ? p.ldc : p.ldn;
-  const int chd = (FORM == 0 ? p.N - n0 : p.C - c0), chg = (FORM == 0 ? p.C - c0 : p.N - n0);   // channels left
-  const bool vecd = FORM == 0 ? p.vec_n : p.vec_c, vecg = FORM == 0 ? p.vec_c : p.vec_n;
-  const int ntaps = p.k * p.k * p.k;
-  const int HV = p.hz * p.hy * p.hx;
-  const int tx = 1 << p.lx, ty = 1 << p.ly;
-
-  f32x16_t acc[MAXT][TN][TC];
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t)
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-      for (int j = 0; j < TC; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][i][j][e] = 0.f;
-
-  // per-wave tap list (wave-uniform; hoisted out of every loop: no integer division inside)
-  int tap_w[MAXT], toff_w[MAXT];
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) {
-    const int tap = p.k == 1 ? (t == 0 ? 0 : ntaps) : wid + 4 * t;
-    tap_w[t] = tap;
-    const int kx = tap % p.k, ky = (tap / p.k) % p.k, kz = tap / (p.k * p.k);
-    toff_w[t] = __builtin_amdgcn_readfirstlane(((kz * p.hy + ky) * p.hx + kx) * PG);
-  }
-  // lane roles for the transposed reads
-  const int g16 = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  const int chan_b = ((g16 & 1) * 16 + 4 * pp) * 2;   // byte offset of this lane's 4 channels in a 32-channel block
-  const int vrow = 8 * (g16 >> 1) + q;                // voxel (within a 16-voxel K step) whose row this lane addresses
-
-  const int tile_begin = xcd_remap(blockIdx.x, gridDim.x) * p.tiles_per_block;
-  int tile_end = tile_begin + p.tiles_per_block;
-  if (tile_end > p.tiles_total) tile_end = p.tiles_total;
-
-  // ---- software pipeline: the next tile's global loads are in flight (registers) while this tile computes ----
-  constexpr int MAXP = 20;                      // 16-byte pieces per thread (host guarantees pieces <= 256 * MAXP)
-  uint4 sv[MAXP];
-  const int ndp = TM * (CDB / 8), ngp = HV * (CGB / 8);
-  auto piece_dst = [&](int piece) -> int {
-    if (piece < ndp) return (piece / (CDB / 8)) * PD + (piece % (CDB / 8)) * 16;
-    const int pg = piece - ndp;
-    return TM * PD + (pg / (CGB / 8)) * PG + (pg % (CGB / 8)) * 16;
-  };
-  auto load_tile = [&](int x0, int y0, int z0) {
-    const int bz = z0 * p.stride - p.pad, by = y0 * p.stride - p.pad, bx = x0 * p.stride - p.pad;
-#pragma unroll
-    for (int u = 0; u < MAXP; ++u) {
-      const int piece = tid + 256 * u;
-      sv[u] = make_uint4(0, 0, 0, 0);
-      if (piece < ndp) {
-        const int row = piece / (CDB / 8), ch = piece % (CDB / 8);
-        const int vx = row & (tx - 1), vy = (row >> p.lx) & (ty - 1), vz = row >> (p.lx + p.ly);
-        const int gz = z0 + vz, gy = y0 + vy, gx = x0 + vx;
-        if (gz < p.Mz && gy < p.My && gx < p.Mx && ch * 8 < chd) {
-          const bf16_t* src = dense + (unsigned)(((gz * p.My + gy) * p.Mx + gx) * ldd + ch * 8);
-          sv[u] = VEC ? *reinterpret_cast<const uint4*>(src) : load8(src, chd - ch * 8, vecd);
-        }
-      } else if (piece < ndp + ngp) {
-        const int pg = piece - ndp;
-        const int row = pg / (CGB / 8), ch = pg % (CGB / 8);
-        const int q1 = (int)__umulhi((unsigned)row, p.m_hx), hzi = (int)__umulhi((unsigned)row, p.m_hxy);
-        const int hxi = row - q1 * p.hx, hyi = q1 - hzi * p.hy;
-        const int gz = bz + hzi, gy = by + hyi, gx = bx + hxi;
-        if ((unsigned)gz < (unsigned)p.Gz && (unsigned)gy < (unsigned)p.Gy && (unsigned)gx < (unsigned)p.Gx && ch * 8 < chg) {
-          const bf16_t* src = gath + (unsigned)(((gz * p.Gy + gy) * p.Gx + gx) * ldg + ch * 8);
-          sv[u] = VEC ? *reinterpret_cast<const uint4*>(src) : load8(src, chg - ch * 8, vecg);
-        }
-      }
-    }
-  };
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int u = 0; u < MAXP; ++u) {
-      const int piece = tid + 256 * u;
-      if (piece < ndp + ngp) *reinterpret_cast<uint4*>(smem + piece_dst(piece)) = sv[u];
-    }
-  };
-
-  int tile = tile_begin, tix = 0, tiy = 0, tiz = 0;
-  while (tile < tile_end && !tile_coords(tile, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++tile;
-  if (tile < tile_end) load_tile(tix << p.lx, tiy << p.ly, tiz << p.lz);
-  while (tile < tile_end) {
-    int nt = tile + 1, ntix = 0, ntiy = 0, ntiz = 0;
-    while (nt < tile_end && !tile_coords(nt, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nt;
-    __syncthreads();   // previous tile's reads are done
-    store_tile();
-    __syncthreads();
-    if (nt < tile_end) load_tile(ntix << p.lx, ntiy << p.ly, ntiz << p.lz);
-    // ---- MFMA over the tile's voxels, 16 per K step ----
-    const int ksteps = TM >> 4;
-    for (int ks = 0; ks < ksteps; ++ks) {
-      if (p.k == 1 && (ks & 3) != wid) continue;     // 1x1x1: the 4 waves share the single tap by K step
-      const int v1 = ks * 16 + vrow, v2 = v1 + 4;
-      const int x1 = v1 & (tx - 1), y1 = (v1 >> p.lx) & (ty - 1), z1 = v1 >> (p.lx + p.ly);
-      const int x2 = v2 & (tx - 1), y2 = (v2 >> p.lx) & (ty - 1), z2 = v2 >> (p.lx + p.ly);
-      const int d1 = v1 * PD + chan_b, d2 = v2 * PD + chan_b;
-      const int g1 = ((z1 * p.stride * p.hy + y1 * p.stride) * p.hx + x1 * p.stride) * PG + chan_b;
-      const int g2 = ((z2 * p.stride * p.hy + y2 * p.stride) * p.hx + x2 * p.stride) * PG + chan_b;
-      constexpr int TD = FORM == 0 ? TN : TC, TG = FORM == 0 ? TC : TN;
-      bf16x8_t df[TD];
-#pragma unroll
-      for (int i = 0; i < TD; ++i) {
-        const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(Dt + d1 + i * 64));
-        const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(Dt + d2 + i * 64));
-        df[i] = (bf16x8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int t = 0; t < MAXT; ++t) {
-        if (tap_w[t] < ntaps) {
-          const int toff = toff_w[t];
-          bf16x8_t gf[TG];
-#pragma unroll
-          for (int j = 0; j < TG; ++j) {
-            const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(Gt + g1 + toff + j * 64));
-            const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(Gt + g2 + toff + j * 64));
-            gf[j] = (bf16x8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          }
-#pragma unroll
-          for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int j = 0; j < TC; ++j) {
-              if (FORM == 0) acc[t][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df[i], gf[j], acc[t][i][j], 0, 0, 0);
-              else acc[t][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gf[i], df[j], acc[t][i][j], 0, 0, 0);
-            }
-        }
-      }
-    }
-    tile = nt; tix = ntix; tiy = ntiy; tiz = ntiz;
-  }
-  // ---- merge into dwk[b][tap][n][c] ----
-  float* wout = p.dwk + (long)b * p.wsb;
-  const int fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < MAXT; ++t) {
-    const int tap = tap_w[t];
-    if (tap < ntaps) {
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TC; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int n = n0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
-            const int c = c0 + j * 32 + fr;
-            if (n < p.N && c < p.C) {
-              if (p.plain) wout[((long)tap * p.N + n) * p.C + c] = acc[t][i][j][e];
-              else atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, acc[t][i][j][e]);
-            }
-          }
-    }
-  }
-}
-
-// =====================================================================================
-// conv_f32_wgrad_k -- the weight gradient in fp32 mode on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32
-// accumulation).  Same block structure as conv_mfma_wgrad_k (one slab of dwk per block, dense tile + gathered halo staged
-// once in LDS as [voxel][channel] fp32 rows, accumulators stationary over the block's tiles), but the MFMA reduces over
-// TWO voxels per instruction and takes one fp32 per lane and operand: lane (index = lane & 31, voxel = lane >> 5) reads
-// its value with a plain ds_read_b32 -- no transposed reads.  An fp32 MFMA occupies the SIMD for 64 cycles, so the LDS
-// reads and the address arithmetic of a voxel pair sit in its shadow; the next pair's fragments are read one step ahead.
-//
-// The 32 indices of the GATHERED operand are (tap, channel) pairs: with >= 32 gathered channels an MFMA tile is one tap
-// x 32 channels (27 tiles); with fewer channels (the 1..16-channel layers of the full-resolution tail) CP = next power
-// of two >= C channels of 32 / CP taps share a tile (14, 7, 4, 2 or 1 tiles instead of 27) -- the tap offset is just a
-// per-lane constant in the gathered read's address.  The tiles are dealt to min(4, tiles) wave groups; with fewer than
-// four tiles the remaining waves split the voxel pairs.  NT = tiles per wave is a template parameter: every wave runs
-// NT unconditional MFMAs per pair (a wave with fewer real tiles recomputes one into an accumulator that is never
-// stored), so the pipeline has no wave-dependent control flow and hipcc keeps its counted lgkmcnt waits.
-// =====================================================================================
-template <int FORM, int NT>
-__global__ __launch_bounds__(256, 1) void conv_f32_wgrad_k(WgradP2 p) {
-  constexpr int PD = 128;                            // dense LDS row pitch (bytes): 32 fp32 channels, zero padded
-  constexpr int MAXP = NT == 7 ? 21 : 24;            // 16-byte staging pieces per thread (host guarantees the fit; with 7 tiles
-                                                     // per wave = 112 accumulator registers 21 is what fits without spilling)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int TM = 1 << (p.lx + p.ly + p.lz);
-  const int PG = p.pg;                               // gathered LDS row pitch (bytes): max(CP, 4) channels
-  char* Dt = smem;
-  char* Gt = smem + TM * PD;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 31, fh = lane >> 5;
-  const int b = blockIdx.z;
-  const int nb = blockIdx.y / p.cblocks, cb = blockIdx.y % p.cblocks;
-  const int n0 = nb * 32, c0 = cb * 32;
-  const float* dyp = reinterpret_cast<const float*>(p.dyp);
-  const float* xp = reinterpret_cast<const float*>(p.xp);
-  const float* dense = (FORM == 0 ? dyp + (long)b * p.sbn + n0 : xp + (long)b * p.sbc + c0);
-  const float* gath = (FORM == 0 ? xp + (long)b * p.sbc + c0 : dyp + (long)b * p.sbn + n0);
-  const int ldd = FORM == 0 ? p.ldn : p.ldc, ldg = FORM == 0 ? p.ldc : p.ldn;
-  const int chd = (FORM == 0 ? p.N - n0 : p.C - c0), chg = (FORM == 0 ? p.C - c0 : p.N - n0);   // channels left
-  const bool vecd = FORM == 0 ? p.vec_n : p.vec_c, vecg = FORM == 0 ? p.vec_c : p.vec_n;
-  const int ntaps = p.k * p.k * p.k;
-  const int HV = p.hz * p.hy * p.hx;
-  const int tx = 1 << p.lx, ty = 1 << p.ly;
-  const int CP = p.cp, lcp = 31 - __builtin_clz(CP), TPT = 32 >> lcp;       // channels per tap in a tile, taps per tile
-  const int ntiles = (ntaps + TPT - 1) / TPT;
-  const int wt = ntiles >= 4 ? 4 : ntiles, ws = 4 / wt;                       // wave groups over tiles x over voxel pairs
-  const int tg = wid % wt, ps = wid / wt;
-
-  f32x16_t acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-
-  // this lane's (tap, channel) in each of the wave's tiles -> byte offset of the gathered read; a lane / tile without a
-  // real (tap, channel) reads tap 0 (its column or row of the accumulator is never stored)
-  int goff[NT];
-  const int gch = fr & (CP - 1);
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int i = tg + wt * t;
-    const int tap = i * TPT + (fr >> lcp);
-    const bool ok = i < ntiles && tap < ntaps && gch < chg;
-    const int tp = ok ? tap : 0;
-    const int kx = tp % p.k, ky = (tp / p.k) % p.k, kz = tp / (p.k * p.k);
-    goff[t] = ((kz * p.hy + ky) * p.hx + kx) * PG + (ok ? gch : 0) * 4;
-    // one tap per tile (>= 32 gathered channels): the tap offset is wave-uniform -> a scalar register, the lane's channel
-    // offset goes into the common lane term
-    if (NT == 7) goff[t] = __builtin_amdgcn_readfirstlane(((kz * p.hy + ky) * p.hx + kx) * PG);
-  }
-
-  const int tile_begin = xcd_remap(blockIdx.x, gridDim.x) * p.tiles_per_block;
-  int tile_end = tile_begin + p.tiles_per_block;
-  if (tile_end > p.tiles_total) tile_end = p.tiles_total;
-
-  // ---- staging: 16-byte pieces (4 channels), the next tile's loads in flight while this tile computes ----
-  uint4 sv[MAXP];
-  const int gpr = PG >> 4;                            // pieces per gathered row
-  const int ndp = TM * 8, ngp = HV * gpr;
-  // A staged piece = 4 channels of which 1..4 exist.  Every load of the tile is issued UNCONDITIONALLY from a clamped
-  // address and nothing touches its result before store_tile: a conditional load (or a mask applied right away) makes
-  // hipcc copy the value after an s_waitcnt vmcnt(0) -- 24 serialised L2 round trips per tile, half the kernel's time.
-  // Validity (inside the volume / inside the tensor's channels) travels as one bit per piece and is applied at the LDS
-  // store.  The vector / element-wise choice is made ONCE around the whole unrolled loop for the same reason.
-  const int lgpr = 31 - __builtin_clz(gpr);           // (gpr = 1, 2, 4 or 8)
-  unsigned long long okbits = 0;
-#define F32WG_LOAD_LOOP(LD4)                                                                                            \
-  _Pragma("unroll") for (int u = 0; u < MAXP; ++u) {                                                                    \
-    const int piece = tid + 256 * u;                                                                                    \
-    const bool isd = 256 * u < ndp;      /* block-uniform: ndp = 8 TM is a multiple of 256 -> scalar base pointers */     \
-    const int pg = piece - ndp;                                                                                         \
-    const int row = isd ? piece >> 3 : pg >> lgpr, ch = isd ? piece & 7 : pg & (gpr - 1);                               \
-    const int vx = row & (tx - 1), vy = (row >> p.lx) & (ty - 1), vz = row >> (p.lx + p.ly);                            \
-    const int q1 = (int)__umulhi((unsigned)row, p.m_hx), hzi = (int)__umulhi((unsigned)row, p.m_hxy);                  \
-    const int gz = isd ? z0 + vz : bz + hzi, gy = isd ? y0 + vy : by + (q1 - hzi * p.hy), gx = isd ? x0 + vx : bx + (row - q1 * p.hx); \
-    const int Lz = isd ? p.Mz : p.Gz, Ly = isd ? p.My : p.Gy, Lx = isd ? p.Mx : p.Gx;                                  \
-    const bool ok = piece < ndp + ngp && (unsigned)gz < (unsigned)Lz && (unsigned)gy < (unsigned)Ly &&                  \
-                    (unsigned)gx < (unsigned)Lx && ch * 4 < (isd ? chd : chg);                                          \
-    const unsigned off = ok ? (unsigned)(((gz * Ly + gy) * Lx + gx) * (isd ? ldd : ldg) + ch * 4) : 0u;                 \
-    const float* src = (isd ? dense : gath) + off;                                                                      \
-    const int nvalid = ok ? (isd ? chd : chg) - ch * 4 : 1; (void)nvalid;                                               \
-    okbits |= (unsigned long long)ok << u;                                                                              \
-    sv[u] = LD4;                                                                                                        \
-    if (u % 6 == 5) __builtin_amdgcn_sched_barrier(0);   /* bound the live address temporaries: 6 loads per group */      \
-  }
-  // (vector loads only: the host sends operands without 16-byte aligned rows to the direct kernel.  A second, element-wise
-  //  copy of this unrolled loop took the 7-tile variant to 78 KB -- past the 64 KB instruction cache two CUs share.)
-  auto load_next = [&](int x0, int y0, int z0) __attribute__((always_inline)) {
-    const int bz = z0 * p.stride - p.pad, by = y0 * p.stride - p.pad, bx = x0 * p.stride - p.pad;
-    okbits = 0;
-    F32WG_LOAD_LOOP(*reinterpret_cast<const uint4*>(src))
-  };
-#undef F32WG_LOAD_LOOP
-  const bool partd = (chd & 3) != 0 && chd < 32, partg = (chg & 3) != 0 && chg < 32;     // a piece with 1..3 valid channels exists
-  auto store_tile = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < MAXP; ++u) {
-      const int piece = tid + 256 * u;
-      if (piece < ndp + ngp) {
-        uint4 v = sv[u];
-        if (!((okbits >> u) & 1)) v = make_uint4(0, 0, 0, 0);
-        if (partd || partg) {       // (block-uniform) channels past the tensor's own: padding or a neighbour's slice -> zero
-          const bool isd = 256 * u < ndp;
-          const int ch = isd ? (piece & 7) : ((piece - ndp) & (gpr - 1));
-          const int nv = (isd ? chd : chg) - ch * 4;
-          if (nv < 4) { v.w = 0; if (nv < 3) v.z = 0; if (nv < 2) v.y = 0; if (nv < 1) v.x = 0; }
-        }
-        reinterpret_cast<uint4*>(smem)[piece] = v;     // dense rows, then halo rows: contiguous
-      }
-    }
-  };
-
-  // one voxel pair (2 q, 2 q + 1: x neighbours of one row) -> the lane's dense value and its tiles' gathered values
-  const int lane_d = fh * PD + fr * 4, lane_g = fh * p.stride * PG + (NT == 7 ? gch * 4 : 0);
-  auto rd = [&](int q, float& d, float (&g)[NT]) {
-    const int v = 2 * q;
-    const int x = v & (tx - 1), y = (v >> p.lx) & (ty - 1), z = v >> (p.lx + p.ly);
-    d = *reinterpret_cast<const float*>(Dt + v * PD + lane_d);
-    const char* gp = Gt + ((z * p.stride * p.hy + y * p.stride) * p.hx + x * p.stride) * PG + lane_g;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) g[t] = *reinterpret_cast<const float*>(gp + goff[t]);
-  };
-  auto mm = [&](float d, const float (&g)[NT]) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      if (FORM == 0) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(d, g[t], acc[t], 0, 0, 0);
-      else acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(g[t], d, acc[t], 0, 0, 0);
-    }
-  };
-
-  const int npairs = TM >> 1;                               // (a multiple of 8)
-  int tile = tile_begin, tix = 0, tiy = 0, tiz = 0;
-  while (tile < tile_end && !tile_coords(tile, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++tile;
-  if (tile < tile_end) load_next(tix << p.lx, tiy << p.ly, tiz << p.lz);
-  while (tile < tile_end) {
-    int nt = tile + 1, ntix = 0, ntiy = 0, ntiz = 0;
-    while (nt < tile_end && !tile_coords(nt, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nt;
-    __syncthreads();   // previous tile's reads are done
-    store_tile();
-    __syncthreads();
-    if (nt < tile_end) load_next(ntix << p.lx, ntiy << p.ly, ntiz << p.lz);
-    float dA, dB, gA[NT], gB[NT];
-    // one pair ahead: the next pair's reads go out in one group behind this pair's MFMAs.  Measured alternatives on the
-    // 32 -> 32 layer at 128^3 (this order: 79-82 TFLOP/s): a row walk with one v_add per read instead of the (x, y, z)
-    // decomposition per pair 62-65; reads strictly alternating with the MFMAs 57-59; hipcc's own order (every read sunk to
-    // its MFMA behind lgkmcnt(0)) 70.
-    rd(ps, dA, gA);
-    for (int q = ps; q < npairs; q += 2 * ws) {
-      rd(q + ws, dB, gB);
-      __builtin_amdgcn_sched_barrier(0);
-      mm(dA, gA);
-      __builtin_amdgcn_sched_barrier(0);
-      rd(q + 2 * ws < npairs ? q + 2 * ws : ps, dA, gA);        // (the last step re-reads pair `ps`: harmless, keeps the loop uniform)
-      __builtin_amdgcn_sched_barrier(0);
-      mm(dB, gB);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    tile = nt; tix = ntix; tiy = ntiy; tiz = ntiz;
-  }
-  // ---- merge into dwk[b][tap][n][c] ----
-  float* wout = p.dwk + (long)b * p.wsb + (long)(blockIdx.x % (unsigned)p.nrep) * p.rep_stride;
-  if constexpr (NT == 7) {
-    // one tap per tile (both forms): row r of the accumulator is output channel n0 + r, the lane's column is input channel
-    // c0 + fr.  One pointer per tile, stepped through the 16 rows (kept compact: the 112 merges of the 7-tile variant
-    // with per-element index arithmetic alone were 13 KB of code)
-    const int c = c0 + fr;
-    const bool full = n0 + 32 <= p.N;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int tap = tg + wt * t;
-      if (tap < ntaps && c < p.C) {
-        float* pe = wout + ((long)tap * p.N + n0 + 4 * fh) * p.C + c;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          if (full || n0 + (e & 3) + 8 * (e >> 2) + 4 * fh < p.N) {
-            if (p.plain) *pe = acc[t][e]; else atomicAdd(pe, acc[t][e]);
-          }
-          pe += ((e & 3) == 3 ? 5 : 1) * p.C;
-        }
-      }
-    }
-  } else {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int r = (e & 3) + 8 * (e >> 2) + 4 * fh;        // accumulator row of this element; the lane's column is fr
-      int tap, n, c;
-      if (FORM == 0) {       // rows = dense n, columns = gathered (tap, c)
-        const int i = tg + wt * t, tp = i * TPT + (fr >> lcp);
-        tap = (i < ntiles && tp < ntaps && gch < chg) ? tp : -1; n = n0 + r; c = c0 + gch;
-      } else {               // rows = gathered (tap, n), columns = dense c: the row's (tap, n) is lane-independent
-        const int i = tg + wt * t, tp = i * TPT + (r >> lcp), nn = r & (CP - 1);
-        tap = (i < ntiles && tp < ntaps && nn < chg) ? tp : -1; n = n0 + nn; c = c0 + fr;
-      }
-      if (tap >= 0 && n < p.N && c < p.C) {
-        if (p.plain) wout[((long)tap * p.N + n) * p.C + c] = acc[t][e];
-        else atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, acc[t][e]);
-      }
-    }
-  }
-  }
-}
-
+// ---- Weight gradients.  conv_mfma_wgrad_k / conv_f32_wgrad_k (32 x 32 tiles, any stride, the tile chosen by wgrad_plan) are
+// in conv_wgrad.hip; here: conv_mfma_wgrad2_k (stride 1, W >= 32), the voxels-along-K kernels, and the dispatch. ----
 // =====================================================================================
 // conv_mfma_wgrad2_k -- stride-1 3x3x3 weight gradient for W >= 32 (any channel counts; one
 // 32(n) x 32(c) slab of dwk per block, thin layers are zero-padded in LDS once).
@@ -3545,14 +3042,6 @@ static bool wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_
          x->W >= 32 && (long)t_vox(x) * x->ld < (1L << 31) && (long)t_vox(dy) * dy->ld < (1L << 31);
 }
 
-// Small weight tensors (the 1..16-channel layers, 1x1x1 gates): a thousand blocks merging into a few cache lines
-// serialise in the L2 atomic unit (1 -> 32 channels at 128^3: 520 us, of which ~400 us were atomics).  Their blocks
-// merge into WGRAD_NREP replicas in the workspace instead, summed by one tiny kernel.
-#define WGRAD_NREP 64
-#define WGRAD_REP_MAX_ELEMS 16384
-static long wgrad_out_elems(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
-  return (long)d->ksize * d->ksize * d->ksize * dy->C * x->C * (d->per_sample_w ? x->B : 1);
-}
 // out[i] = sum over the replicas.  A few thousand outputs x 64 replicas: the serial 64-load walk per thread this replaces was
 // latency-bound (17.7 us per launch, 13 launches per step); here 8 lanes share an output (8 independent loads each) and
 // fold through a wave shuffle.
@@ -3566,6 +3055,11 @@ __global__ __launch_bounds__(256) void wgrad_replica_sum_k(const float* __restri
   }
   a += __shfl_xor(a, 4, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 1, 64);
   if (part == 0 && i < n) out[i] = a;
+}
+int wgrad_replica_sum(const float* rep, long wsz, float* dwk, hipStream_t s) {
+  hipLaunchKernelGGL(wgrad_replica_sum_k, dim3((unsigned)((wsz + 31) / 32)), dim3(256), 0, s, rep, WGRAD_NREP, wsz, dwk);
+  COMA_LAUNCH_CHECK();
+  return 0;
 }
 
 // =====================================================================================
@@ -3924,13 +3418,8 @@ static int conv_thin16_wgrad(const coma_conv_desc* d, const coma_tensor* x, cons
   q.dy = (const bf16_t*)dy->data; q.ldn = (int)dy->ld; q.sbn = dy->sb; q.N = dy->C;
   q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 2);
   q.dbytes = (unsigned)((unsigned long long)t_vox(dy) * dy->ld * 2);
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
-  int gx = 512 / x->B;
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, x->B);
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
   const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
@@ -3942,17 +3431,13 @@ static int conv_thin16_wgrad(const coma_conv_desc* d, const coma_tensor* x, cons
   const int nm = cp == 16 ? 27 : 14;
   size_t lds = (size_t)(34 * 6 * 4 + 2) * cp * 2 + (size_t)256 * nb * 16 * 2;
   if (lds < (size_t)nm * nb * 256 * 4) lds = (size_t)nm * nb * 256 * 4;
-  const dim3 grid((unsigned)gx, 1, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
   coma_set_kernel_tag("conv_thin16_wgrad_k<%d, %d>", cp, nb);
   if (cp == 16) hipLaunchKernelGGL((conv_thin16_wgrad_k<16, 1>), grid, dim3(256), lds, s, q);
   else if (nb == 2) hipLaunchKernelGGL((conv_thin16_wgrad_k<8, 2>), grid, dim3(256), lds, s, q);
   else hipLaunchKernelGGL((conv_thin16_wgrad_k<8, 1>), grid, dim3(256), lds, s, q);
   COMA_LAUNCH_CHECK();
-  if (replicas) {
-    hipLaunchKernelGGL(wgrad_replica_sum_k, dim3((unsigned)((wsz + 31) / 32)), dim3(256), 0, s, (const float*)ws, WGRAD_NREP, wsz, dwk);
-    COMA_LAUNCH_CHECK();
-  }
-  return 0;
+  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
 }
 
 // =====================================================================================
@@ -4110,32 +3595,22 @@ static int conv_f32_wgrad16(const coma_conv_desc* d, const coma_tensor* x, const
   q.dbytes = (unsigned)((unsigned long long)t_vox(dn) * dn->ld * 4);
   q.gbytes = (unsigned)((unsigned long long)t_vox(ga) * ga->ld * 4);
   const int S = d->stride, tz = S == 1 ? 2 : 1, ty = S == 1 ? 4 : 2;
-  q.ntx = (q.Mx + 31) / 32; q.nty = (q.My + ty - 1) / ty; q.ntz = (q.Mz + tz - 1) / tz;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   q.cblocks = q.C / 32;
   const int pairs = q.cblocks * (q.N / 32);
-  int gx = 256 / (pairs * x->B);
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.Mz, q.My, q.Mx, 32, ty, tz, 256, pairs * x->B);
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
   q.dwk = dwk;
   if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
   const size_t lds = S == 1 ? (size_t)(34 * 6 * 4 + 256) * 32 * 4 : (size_t)(65 * 5 * 3 + 64) * 32 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_f32_wgrad16_k<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_f32_wgrad16_k<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_f32_wgrad16_k<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  const dim3 grid((unsigned)gx, (unsigned)pairs, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, (unsigned)pairs, (unsigned)x->B);
   coma_set_kernel_tag("conv_f32_wgrad16_k<%d, %d>", S, d->form);
-  if (S == 1) hipLaunchKernelGGL((conv_f32_wgrad16_k<1, 0>), grid, dim3(256), lds, s, q);
-  else if (d->form == 0) hipLaunchKernelGGL((conv_f32_wgrad16_k<2, 0>), grid, dim3(256), lds, s, q);
-  else hipLaunchKernelGGL((conv_f32_wgrad16_k<2, 1>), grid, dim3(256), lds, s, q);
+#define W16(S_, F_) do { set_max_lds<conv_f32_wgrad16_k<S_, F_>>(); hipLaunchKernelGGL((conv_f32_wgrad16_k<S_, F_>), grid, dim3(256), lds, s, q); } while (0)
+  if (S == 1) W16(1, 0);
+  else if (d->form == 0) W16(2, 0);
+  else W16(2, 1);
+#undef W16
   COMA_LAUNCH_CHECK();
   return 0;
 }
@@ -4319,40 +3794,29 @@ static int conv_bf16_wgrad16(const coma_conv_desc* d, const coma_tensor* x, cons
   q.dbytes = (unsigned)((unsigned long long)t_vox(dn) * dn->ld * 2);
   q.gbytes = (unsigned)((unsigned long long)t_vox(ga) * ga->ld * 2);
   const int S = d->stride, tz = S == 1 ? 2 : 1, ty = S == 1 ? 4 : 2;
-  q.ntx = (q.Mx + 31) / 32; q.nty = (q.My + ty - 1) / ty; q.ntz = (q.Mz + tz - 1) / tz;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
   q.cblocks = q.C / 32;
   const int pairs = q.cblocks * (q.N / 32);
-  int gx = 256 / (pairs * x->B);
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.Mz, q.My, q.Mx, 32, ty, tz, 256, pairs * x->B);
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
   q.dwk = dwk;
   if (!(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
   const size_t lds = S == 1 ? (size_t)(34 * 6 * 4 + 256) * 64 : (size_t)(65 * 5 * 3 + 64) * 64;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_bf16_wgrad16_k<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_bf16_wgrad16_k<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_bf16_wgrad16_k<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr = true;
-  }
-  const dim3 grid((unsigned)gx, (unsigned)pairs, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, (unsigned)pairs, (unsigned)x->B);
   coma_set_kernel_tag("conv_bf16_wgrad16_k<%d, %d>", S, d->form);
-  if (S == 1) hipLaunchKernelGGL((conv_bf16_wgrad16_k<1, 0>), grid, dim3(256), lds, s, q);
-  else if (d->form == 0) hipLaunchKernelGGL((conv_bf16_wgrad16_k<2, 0>), grid, dim3(256), lds, s, q);
-  else hipLaunchKernelGGL((conv_bf16_wgrad16_k<2, 1>), grid, dim3(256), lds, s, q);
+#define W16(S_, F_) do { set_max_lds<conv_bf16_wgrad16_k<S_, F_>, 80>(); hipLaunchKernelGGL((conv_bf16_wgrad16_k<S_, F_>), grid, dim3(256), lds, s, q); } while (0)
+  if (S == 1) W16(1, 0);
+  else if (d->form == 0) W16(2, 0);
+  else W16(2, 1);
+#undef W16
   COMA_LAUNCH_CHECK();
   return 0;
 }
 
 static bool thin16f_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
-  static const bool on = []{ const char* e = getenv("COMA_THIN16F"); return !(e && e[0] == '0'); }();
   const int nmax = x->C <= 4 ? 32 : 16;
-  return on && d->form == 0 && d->ksize == 3 && d->stride == 1 && x->dtype == COMA_F32 && dy->dtype == COMA_F32 && x->W >= 32 &&
+  return thin16f_on() && d->form == 0 && d->ksize == 3 && d->stride == 1 && x->dtype == COMA_F32 && dy->dtype == COMA_F32 && x->W >= 32 &&
          x->C <= 16 && dy->C <= nmax && x->ld % 4 == 0 && x->sb % 4 == 0 && dy->ld % 4 == 0 && dy->sb % 4 == 0 &&
          (!x->data || aligned16(x->data)) && (!dy->data || aligned16(dy->data)) &&
          (unsigned long long)t_vox(x) * x->ld * 4 < 0x7fff0000ull && (unsigned long long)t_vox(dy) * dy->ld * 4 < 0x7fff0000ull;
@@ -4365,13 +3829,8 @@ static int conv_thin16f_wgrad(const coma_conv_desc* d, const coma_tensor* x, con
   q.dy = (const float*)dy->data; q.ldn = (int)dy->ld; q.sbn = dy->sb; q.N = dy->C;
   q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
   q.dbytes = (unsigned)((unsigned long long)t_vox(dy) * dy->ld * 4);
-  q.ntx = (q.W + 31) / 32; q.nty = (q.H + 3) / 4; q.ntz = (q.D + 1) / 2;
-  q.ids_total = q.ntx * q.nty * ((q.ntz + 7) / 8) * 8;
-  int gx = (q.C > 8 ? 256 : 512) / x->B;
-  if (gx < 1) gx = 1;
-  if (gx > q.ids_total) gx = q.ids_total;
-  q.ids_per_block = (q.ids_total + gx - 1) / gx;
-  gx = (q.ids_total + q.ids_per_block - 1) / q.ids_per_block;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, q.C > 8 ? 256 : 512, x->B);
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
   const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
@@ -4383,26 +3842,16 @@ static int conv_thin16f_wgrad(const coma_conv_desc* d, const coma_tensor* x, con
   const int nm = (27 + 16 / cp - 1) / (16 / cp);
   size_t lds = (size_t)34 * 6 * 4 * cp * 4 + (size_t)256 * nb * 16 * 4;
   if (lds < (size_t)nm * nb * 256 * 4) lds = (size_t)nm * nb * 256 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_wgrad_k<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_wgrad_k<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_wgrad_k<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_thin16f_wgrad_k<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr = true;
-  }
-  const dim3 grid((unsigned)gx, 1, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
   coma_set_kernel_tag("conv_thin16f_wgrad_k<%d, %d>", cp, nb);
-  if (cp == 16) hipLaunchKernelGGL((conv_thin16f_wgrad_k<16, 1>), grid, dim3(256), lds, s, q);
-  else if (cp == 8) hipLaunchKernelGGL((conv_thin16f_wgrad_k<8, 1>), grid, dim3(256), lds, s, q);
-  else if (nb == 2) hipLaunchKernelGGL((conv_thin16f_wgrad_k<4, 2>), grid, dim3(256), lds, s, q);
-  else hipLaunchKernelGGL((conv_thin16f_wgrad_k<4, 1>), grid, dim3(256), lds, s, q);
+#define T16FW(CP_, NB_) do { set_max_lds<conv_thin16f_wgrad_k<CP_, NB_>, 80>(); hipLaunchKernelGGL((conv_thin16f_wgrad_k<CP_, NB_>), grid, dim3(256), lds, s, q); } while (0)
+  if (cp == 16) T16FW(16, 1);
+  else if (cp == 8) T16FW(8, 1);
+  else if (nb == 2) T16FW(4, 2);
+  else T16FW(4, 1);
+#undef T16FW
   COMA_LAUNCH_CHECK();
-  if (replicas) {
-    hipLaunchKernelGGL(wgrad_replica_sum_k, dim3((unsigned)((wsz + 31) / 32)), dim3(256), 0, s, (const float*)ws, WGRAD_NREP, wsz, dwk);
-    COMA_LAUNCH_CHECK();
-  }
-  return 0;
+  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
 }
 
 static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
@@ -4411,8 +3860,6 @@ static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const
   p.dyp = (const bf16_t*)dy->data; p.ldn = (int)dy->ld; p.sbn = dy->sb;
   p.xp = (const bf16_t*)x->data; p.ldc = (int)x->ld; p.sbc = x->sb;
   p.N = dy->C; p.C = x->C; p.D = x->D; p.H = x->H; p.W = x->W;
-  p.ntx = (p.W + 31) / 32; p.nty = (p.H + 3) / 4; p.ntz = (p.D + 1) / 2;
-  p.tiles_total = p.ntx * p.nty * ((p.ntz + 7) / 8) * 8;
   p.cblocks = (p.C + 31) / 32;
   {   // live 8-channel chunks per staged row, rounded up to 1 / 2 / 4 (blocks of a wide operand always see 4)
     const int nd = p.N > 32 ? 4 : (p.N + 7) / 8, ng = p.C > 32 ? 4 : (p.C + 7) / 8;
@@ -4423,11 +3870,8 @@ static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const
   p.vec_c = x->ld % 8 == 0 && x->sb % 8 == 0 && (((uintptr_t)x->data) & 15) == 0;
   // 512 blocks = the 2 resident blocks per CU, once: every block ends with a 27 x 32 x 32 fp32 atomic merge, and a second
   // round of blocks doubled that traffic (64 -> 64 at 64^3: 215 -> 156 us, 128 -> 128 at 32^3: 136 -> 101 us)
-  int chunks = 512 / (pairs * x->B);
-  if (chunks < 1) chunks = 1;
-  if (chunks > p.tiles_total) chunks = p.tiles_total;
-  p.tiles_per_block = (p.tiles_total + chunks - 1) / chunks;
-  chunks = (p.tiles_total + p.tiles_per_block - 1) / p.tiles_per_block;
+  const TileRun r = tile_run(p.D, p.H, p.W, 32, 4, 2, 512, pairs * x->B);
+  p.ntx = r.ntx; p.nty = r.nty; p.ntz = r.ntz; p.tiles_total = r.ids_total; p.tiles_per_block = r.ids_per_block;
   const long taps = (long)d->ksize * d->ksize * d->ksize;
   p.dwk = dwk; p.wsb = d->per_sample_w ? taps * p.N * p.C : 0;
   const long wsz = taps * p.N * p.C * (d->per_sample_w ? x->B : 1);
@@ -4437,118 +3881,23 @@ static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const
   if (replicas) p.dwk = (float*)ws;
   if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(p.dwk, 0, sizeof(float) * wsz * p.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
   const size_t lds = (size_t)(256 + (d->ksize == 3 ? 816 + 1 : 256)) * 64;   // +1 row: the unused packed column reads one voxel past the halo
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<0, 2, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<1, 2, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<0, 2, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<1, 2, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<0, 2, 3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad2_k<1, 2, 3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr = true;
-  }
   const bool vec = p.vec_n && p.vec_c && p.N % 8 == 0 && p.C % 8 == 0;
-  const dim3 grid((unsigned)chunks, (unsigned)pairs, (unsigned)x->B);
+  const dim3 grid((unsigned)r.gx, (unsigned)pairs, (unsigned)x->B);
   coma_set_kernel_tag("conv_mfma_wgrad2_k<%d, 2, %d, %d>", (int)vec, d->ksize, d->ksize == 1 ? 1 : p.C <= 8 ? 4 : p.C <= 16 ? 2 : 1);
-#define WG2(K_, PK_) do { if (vec) hipLaunchKernelGGL((conv_mfma_wgrad2_k<1, 2, K_, PK_>), grid, dim3(256), lds, s, p); \
-                          else hipLaunchKernelGGL((conv_mfma_wgrad2_k<0, 2, K_, PK_>), grid, dim3(256), lds, s, p); } while (0)
+#define WG2_(V_, K_, PK_) do { set_max_lds<conv_mfma_wgrad2_k<V_, 2, K_, PK_>, 80>(); hipLaunchKernelGGL((conv_mfma_wgrad2_k<V_, 2, K_, PK_>), grid, dim3(256), lds, s, p); } while (0)
+#define WG2(K_, PK_) do { if (vec) WG2_(1, K_, PK_); else WG2_(0, K_, PK_); } while (0)
   if (d->ksize == 1) WG2(1, 1);
   else if (p.C <= 8) WG2(3, 4);
   else if (p.C <= 16) WG2(3, 2);
   else WG2(3, 1);
 #undef WG2
+#undef WG2_
   COMA_LAUNCH_CHECK();
-  if (replicas) {
-    hipLaunchKernelGGL(wgrad_replica_sum_k, dim3((unsigned)((wsz + 31) / 32)), dim3(256), 0, s, (const float*)ws, WGRAD_NREP, wsz, dwk);
-    COMA_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-static int ilog2_ceil(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-struct WgradPlan { WgradP2 p; int TM; size_t lds; int tn, tc; dim3 grid; bool ok; };
-
-static WgradPlan wgrad_plan(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
-  WgradPlan pl{};
-  pl.ok = false;
-  const bool f32 = x->dtype == COMA_F32 && dy->dtype == COMA_F32;
-  if (!f32 && (x->dtype != COMA_BF16 || dy->dtype != COMA_BF16)) return pl;
-  if (d->ksize != 3 && d->ksize != 1) return pl;
-  if ((long)t_vox(x) * x->ld >= (1L << 31) || (long)t_vox(dy) * dy->ld >= (1L << 31)) return pl;
-  if (d->form == 1 && d->stride != 2) return pl;
-  WgradP2& p = pl.p;
-  p.dyp = dy->data; p.ldn = (int)dy->ld; p.sbn = dy->sb;
-  p.xp = x->data; p.ldc = (int)x->ld; p.sbc = x->sb;
-  p.N = dy->C; p.C = x->C;
-  const coma_tensor* dn = d->form == 0 ? dy : x;     // dense
-  const coma_tensor* ga = d->form == 0 ? x : dy;     // gathered
-  p.Mz = dn->D; p.My = dn->H; p.Mx = dn->W; p.Gz = ga->D; p.Gy = ga->H; p.Gx = ga->W;
-  p.k = d->ksize; p.stride = d->stride; p.pad = d->pad;
-  const int vq = f32 ? 4 : 8;                        // elements per 16-byte piece
-  p.vec_n = dy->ld % vq == 0 && dy->sb % vq == 0 && (!dy->data || aligned16(dy->data));
-  p.vec_c = x->ld % vq == 0 && x->sb % vq == 0 && (!x->data || aligned16(x->data));
-  pl.tn = (dy->C > 32 && !(x->C > 32 && x->C > dy->C)) ? 2 : 1;
-  pl.tc = (pl.tn == 1 && x->C > 32) ? 2 : 1;
-  if (f32) pl.tn = pl.tc = 1;
-  const int gch = d->form == 0 ? x->C : dy->C;
-  // bytes per element, channels per piece, 16-byte staging pieces per thread
-  const int esz = f32 ? 4 : 2, ppc = f32 ? 4 : 8, maxp = f32 ? ((gch >= 32 && d->ksize == 3) ? 21 : 24) : 20;
-  // fp32 kernel: the gathered operand's 32 MFMA indices are (tap, channel) pairs -- cp channels (a power of two) per tap
-  p.cp = 32; p.pg = 128;
-  if (f32 && gch < 32) { p.cp = 1; while (p.cp < gch) p.cp <<= 1; p.pg = (p.cp < 4 ? 4 : p.cp) * 4; }
-  if (f32 && !(p.vec_n && p.vec_c)) return pl;        // fp32 kernel: 16-byte staging loads only
-  // tile: up to 256 dense voxels at stride 1, 64 at stride 2 (the halo grows 8x); shrink until the LDS image
-  // and the per-thread register staging budget (20 x 16-byte pieces) fit
-  const int cdb = 32 * (d->form == 0 ? pl.tn : pl.tc), cgb = f32 ? p.pg / 4 : 32 * (d->form == 0 ? pl.tc : pl.tn);
-  bool fits = false;
-  for (int budget = d->stride == 1 ? 8 : 6; budget >= 4 && !fits; --budget) {
-    int lx = ilog2_ceil(p.Mx); if (lx > 5) lx = 5;
-    if (d->stride == 2 && lx > 4) lx = 4;
-    if (lx > budget) lx = budget;
-    int rem = budget - lx;
-    int ly = ilog2_ceil(p.My); if (ly > (rem + 1) / 2) ly = (rem + 1) / 2;
-    rem -= ly;
-    int lz = ilog2_ceil(p.Mz); if (lz > rem) lz = rem;
-    while (lx + ly + lz < 4) ++lx;     // at least one 16-voxel K step
-    p.lx = lx; p.ly = ly; p.lz = lz;
-    pl.TM = 1 << (lx + ly + lz);
-    p.hz = ((1 << lz) - 1) * p.stride + p.k; p.hy = ((1 << ly) - 1) * p.stride + p.k; p.hx = ((1 << lx) - 1) * p.stride + p.k;
-    pl.lds = (size_t)pl.TM * cdb * esz + (size_t)p.hz * p.hy * p.hx * cgb * esz + (f32 ? 1024 : 0);
-    fits = pl.lds <= 160 * 1024 && pl.TM * (cdb / ppc) + p.hz * p.hy * p.hx * (cgb / ppc) <= 256 * maxp;
-  }
-  if (!fits) return pl;
-  p.ntx = (p.Mx + (1 << p.lx) - 1) >> p.lx; p.nty = (p.My + (1 << p.ly) - 1) >> p.ly; p.ntz = (p.Mz + (1 << p.lz) - 1) >> p.lz;
-  p.tiles_total = p.ntx * p.nty * ((p.ntz + 7) / 8) * 8;   // ids incl. z padding (tile_coords)
-  p.m_hx = (unsigned)((1ull << 32) / (unsigned)p.hx) + 1u;
-  p.m_hxy = (unsigned)((1ull << 32) / (unsigned)(p.hx * p.hy)) + 1u;
-  p.cblocks = (p.C + 32 * pl.tc - 1) / (32 * pl.tc);
-  const int pairs = ((p.N + 32 * pl.tn - 1) / (32 * pl.tn)) * p.cblocks;
-  // one block per CU, ONE round (256 blocks): a second round repeats every block's 27 x n x c fp32 atomic merge
-  // (32 -> 64 stride 2 at 128^3: 307 -> 254 us; 256 -> 256 at 16^3: 163 -> 107 us)
-  int chunks = 256 / (pairs * x->B);
-  // Deepest layers (>= 64 weight tiles, <= 1024 voxels): ONE block per tile and sample.  With per-sample weights (or one sample) every
-  // dwk element then has a single producer: plain stores instead of memset + fp32 atomics (512 -> 512 at 8^3: the
-  // 28 M atomics of a 2-chunk split cost ~90 of the kernel's 142 us).
-  // (measured: at <= 1024 dense voxels a quarter of the CUs busy without atomics beats all of them with; at 4096
-  // voxels the single block's MFMA work is the longer pole and the old split wins)
-  if (pairs * x->B >= 64 && (long)p.Mz * p.My * p.Mx <= 1024) chunks = 1;
-  if (chunks < 1) chunks = 1;
-  if (chunks > p.tiles_total) chunks = p.tiles_total;
-  p.tiles_per_block = (p.tiles_total + chunks - 1) / chunks;
-  chunks = (p.tiles_total + p.tiles_per_block - 1) / p.tiles_per_block;
-  p.plain = chunks == 1 && (d->per_sample_w || x->B == 1);
-  if (f32 && p.cp < 8 && d->ksize == 3) p.plain = 0;     // fewer than 4 MFMA tiles: several waves of a block sum the same outputs
-  if (f32 && d->ksize == 1) p.plain = 0;                  // 1x1x1: the four waves split the voxel pairs of the single tile
-  pl.grid = dim3((unsigned)chunks, (unsigned)pairs, (unsigned)x->B);
-  const long taps = (long)d->ksize * d->ksize * d->ksize;
-  p.wsb = d->per_sample_w ? taps * p.N * p.C : 0;
-  pl.ok = true;
-  return pl;
+  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
 }
 
 bool conv_mfma_wgrad_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
-  return wgrad2_ok(d, x, dy) || thin16f_wgrad_ok(d, x, dy) || wgrad_plan(d, x, dy).ok;      // (bf16 and fp32: the plan checks the dtype pair)
+  return wgrad2_ok(d, x, dy) || thin16f_wgrad_ok(d, x, dy) || wgrad_plan_ok(d, x, dy);      // (bf16 and fp32: the plan checks the dtype pair)
 }
 size_t conv_mfma_wgrad_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   const long wsz = wgrad_out_elems(d, x, dy);
@@ -4564,66 +3913,7 @@ int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_te
   if (wgrad2_ok(d, x, dy)) return conv_mfma_wgrad2(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   if (thin16f_wgrad_ok(d, x, dy)) return conv_thin16f_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   if (f32_wgrad16_ok(d, x, dy)) return conv_f32_wgrad16(d, x, dy, dwk, s, zeroed);
-  WgradPlan pl = wgrad_plan(d, x, dy);
-  COMA_CHECK(pl.ok, "conv_mfma_wgrad: unsupported problem");
-  pl.p.dwk = dwk;
-  const long wsz = (long)d->ksize * d->ksize * d->ksize * dy->C * x->C * (d->per_sample_w ? x->B : 1);
-  if (!pl.p.plain && !(zeroed & COMA_ZEROED_OUT) && hipMemsetAsync(dwk, 0, sizeof(float) * wsz, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
-  if (x->dtype == COMA_F32) {
-    // small outputs (the 1..16-channel layers): hundreds of blocks merging into a few cache lines serialise in the
-    // atomic unit -- they merge into WGRAD_NREP replicas in the workspace, summed by one small kernel (as wgrad2 does)
-    const bool replicas = !pl.p.plain && wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-    pl.p.nrep = replicas ? WGRAD_NREP : 1;
-    pl.p.rep_stride = replicas ? wsz : 0;
-    if (replicas) {
-      pl.p.dwk = (float*)ws;
-      if (!(zeroed & COMA_ZEROED_WS) && hipMemsetAsync(ws, 0, sizeof(float) * wsz * WGRAD_NREP, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
-    }
-    const int taps = d->ksize * d->ksize * d->ksize, tpt = 32 / pl.p.cp, ntiles = (taps + tpt - 1) / tpt;
-    const int nt = (ntiles + 3) / 4;                  // tiles per wave: 27 -> 7, 14 -> 4, 7 -> 2, <= 4 -> 1
-    static bool attr = false;
-    if (!attr) {
-#define F32ATTR(F, N_) (void)hipFuncSetAttribute((const void*)conv_f32_wgrad_k<F, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      F32ATTR(0, 1); F32ATTR(0, 2); F32ATTR(0, 4); F32ATTR(0, 7); F32ATTR(1, 1); F32ATTR(1, 2); F32ATTR(1, 4); F32ATTR(1, 7);
-#undef F32ATTR
-      attr = true;
-    }
-    coma_set_kernel_tag("conv_f32_wgrad_k<%d, %d>", d->form, nt == 1 ? 1 : nt == 2 ? 2 : nt <= 4 ? 4 : 7);
-#define F32WL(F) do { if (nt == 1) hipLaunchKernelGGL((conv_f32_wgrad_k<F, 1>), pl.grid, dim3(256), pl.lds, s, pl.p); \
-                      else if (nt == 2) hipLaunchKernelGGL((conv_f32_wgrad_k<F, 2>), pl.grid, dim3(256), pl.lds, s, pl.p); \
-                      else if (nt <= 4) hipLaunchKernelGGL((conv_f32_wgrad_k<F, 4>), pl.grid, dim3(256), pl.lds, s, pl.p); \
-                      else hipLaunchKernelGGL((conv_f32_wgrad_k<F, 7>), pl.grid, dim3(256), pl.lds, s, pl.p); } while (0)
-    if (d->form == 0) F32WL(0); else F32WL(1);
-#undef F32WL
-    COMA_LAUNCH_CHECK();
-    if (replicas) {
-      hipLaunchKernelGGL(wgrad_replica_sum_k, dim3((unsigned)((wsz + 31) / 32)), dim3(256), 0, s, (const float*)ws, WGRAD_NREP, wsz, dwk);
-      COMA_LAUNCH_CHECK();
-    }
-    return 0;
-  }
-  const bool vecall = pl.p.vec_n && pl.p.vec_c && dy->C % 8 == 0 && x->C % 8 == 0;
-#define WL(TNV, TCV, F)                                                                                          \
-  do {                                                                                                           \
-    if (vecall) {                                                                                                \
-      (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_k<TNV, TCV, F, 1>,                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      hipLaunchKernelGGL((conv_mfma_wgrad_k<TNV, TCV, F, 1>), pl.grid, dim3(256), pl.lds, s, pl.p);              \
-    } else {                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)conv_mfma_wgrad_k<TNV, TCV, F, 0>,                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                         \
-      hipLaunchKernelGGL((conv_mfma_wgrad_k<TNV, TCV, F, 0>), pl.grid, dim3(256), pl.lds, s, pl.p);              \
-    }                                                                                                            \
-  } while (0)
-  coma_set_kernel_tag("conv_mfma_wgrad_k<%d, %d, %d, %d>", pl.tn, pl.tc, d->form, (int)vecall);
-  if (d->form == 0) {
-    if (pl.tn == 2) WL(2, 1, 0); else if (pl.tc == 2) WL(1, 2, 0); else WL(1, 1, 0);
-  } else {
-    if (pl.tn == 2) WL(2, 1, 1); else if (pl.tc == 2) WL(1, 2, 1); else WL(1, 1, 1);
-  }
-#undef WL
-  COMA_LAUNCH_CHECK();
-  return 0;
+  return conv_wgrad_planned(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
 }
 
 // the fp32 problems conv_mfma_halo<float> runs on conv_mfma_halo2_k<2, 16, 1, 1, float>: what conv_split.hip takes under algo 4

@@ -16,24 +16,7 @@
 //   conv_split_tconv_k  -- stride-2 3x3x3 transposed convolution / data gradient of the stride-2 convolutions
 //                          (the problems of conv_mfma_tconv_k<float, *>)
 //   conv_split_wgrad2_k -- stride-2 and transposed 3x3x3 weight gradient (the problems of conv_f32_wgrad16_k<2, *>)
-#include "common.h"
-#include "conv_tiles.h"
-
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-
-// conv_mfma.hip: the fp32 problems its kernels take (halo-tiled at W >= 32; transposed stride-2; stride-2 weight gradients)
-bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
-bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// every kernel here asks for more dynamic LDS than the 64 KB default: raise the kernel's limit to the CU's 160 KB, once
-template <auto KERNEL> static void set_max_lds() {
-  static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)once;
-}
+#include "conv_mfma.h"    // s4_t / lds_s4_t, aligned16, conv_f32_*_problem: the fp32 problems the exact kernels take
 
 // 4 fp32 (one 16-byte staging piece) -> 4 bf16 hi + 4 bf16 lo
 __device__ __forceinline__ void split4(const uint4& v, uint2& hi, uint2& lo) {

@@ -1,4 +1,4 @@
-// Helpers shared by the halo-tiled convolution kernels (conv_mfma.hip, conv_split.hip).
+// Helpers shared by the tiled convolution kernels (the conv_mfma.h family of files, conv_split.hip).
 #pragma once
 #include "common.h"
 
@@ -16,6 +16,13 @@ static inline TileRun tile_run(int D, int H, int W, int tx, int ty, int tz, int 
   r.ids_per_block = (r.ids_total + r.gx - 1) / r.gx;
   r.gx = (r.ids_total + r.ids_per_block - 1) / r.ids_per_block;      // (no block without an id)
   return r;
+}
+
+// a kernel that asks for more dynamic LDS than the 64 KB default: raise its limit to KB kilobytes (160: the whole CU's; 80:
+// half, for two blocks per CU), once per kernel instance
+template <auto KERNEL, int KB = 160> static void set_max_lds() {
+  static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, KB * 1024);
+  (void)once;
 }
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // 8 bf16 = one MFMA A/B fragment

@@ -1,7 +1,7 @@
 # Diagnostic builds of conv_mfma_duo_k (outputs are wrong; never shipped): what a phase costs without the matrix work, without
 # the staging group's work, without the tile epilogue.  Run on the GPU box: bash profiles/ablate_duo.sh
 cd $GRAFT_REPO_ROOT/coma_unet_amd/csrc
-OBJ="api.o conv_direct.o conv_point1.o norm.o gate.o elementwise.o weights.o metrics.o comm.o"
+OBJ="api.o conv_direct.o conv_point1.o conv_wgrad.o conv_split.o norm.o gate.o elementwise.o weights.o metrics.o comm.o"
 for v in NO_MFMA NO_STAGE NO_EPI; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -DCOMA_DUO_$v -c conv_mfma.hip -o /tmp/cm_$v.o 2>/dev/null &
 done

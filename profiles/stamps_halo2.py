@@ -17,13 +17,17 @@ a = ap.parse_args()
 out = os.path.join(ROOT, "gpurun_out", "stamps")
 os.makedirs(out, exist_ok=True)
 lib = os.path.join(out, "libcoma_unet_stamps.so")
-srcs = ["api.hip", "conv_direct.hip", "conv_point1.hip", "conv_mfma.hip", "norm.hip", "elementwise.hip", "weights.hip", "metrics.hip", "comm.hip"]
+import importlib.util      # (the build script by path: importing the package would load the shipped library first)
+_spec = importlib.util.spec_from_file_location("coma_build", os.path.join(ROOT, "coma_unet_amd", "build.py"))
+_build = importlib.util.module_from_spec(_spec); _spec.loader.exec_module(_build)
+srcs = _build.SOURCES
+STAMPED = "conv_mfma.hip"      # conv_mfma_halo2_k and conv_thin16_k, the kernels that carry the stamps
 objs = []
 procs = []
 for s_ in srcs:
     o = os.path.join(out, s_.replace(".hip", ".o")); objs.append(o)
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-c", os.path.join(ROOT, "coma_unet_amd", "csrc", s_), "-o", o]
-    if s_ == "conv_mfma.hip":
+    if s_ == STAMPED:
         if not a.no_stamps:
             cmd.insert(1, "-DCOMA_STAMPS")
         for d_ in a.define:

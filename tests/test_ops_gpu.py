@@ -971,6 +971,26 @@ DISPATCH_ROWS = [
     (32, 16, 1, 1, False, (8, 16, 32), torch.bfloat16, "conv_mfma_pw_k<2, 1>", "conv_mfma_pw_k<1, 1>", "conv_mfma_wgrad2_k<1, 2, 1, 1>"),
     (32, 32, 3, 1, False, (4, 8, 32), torch.float32, "conv_mfma_halo2_k<2, 16, 1, 1, float>", "conv_mfma_halo2_k<2, 16, 1, 1, float>", "conv_f32_wgrad16_k<1, 0>"),
     (128, 64, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_mfma_gather_k<64, 1, __bf16>", "conv_mfma_gather_k<128, 0, __bf16>", None),
+    # the first-generation halo kernel at W = 16 and W = 8 (channel counts the two-group kernel does not take; fp32)
+    (32, 48, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_halo_k<32, 4, 1, __bf16>", "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
+    (32, 32, 3, 1, False, (4, 8, 16), torch.float32, "conv_mfma_halo_k<16, 4, 1, float>", "conv_mfma_halo_k<16, 4, 1, float>", "conv_f32_wgrad_k<0, 7>"),
+    (48, 48, 3, 1, False, (4, 8, 8), torch.bfloat16, "conv_mfma_halo_k<32, 3, 0, __bf16>", "conv_mfma_halo_k<32, 3, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
+    (16, 16, 3, 1, False, (4, 8, 8), torch.float32, "conv_mfma_halo_k<16, 3, 1, float>", "conv_mfma_halo_k<16, 3, 1, float>", "conv_f32_wgrad_k<0, 4>"),
+    # the two-group kernel on the 16-wide grids; conv_mfma_halo2_k where it refuses (N % 32 != 0) and on the thin layers conv_thin16_k leaves
+    (32, 32, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_duo_k<0, 4>", "conv_mfma_duo_k<0, 4>", "conv_mfma_wgrad_k<1, 1, 0, 1>"),
+    (16, 32, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_halo2_k<1, 32, 1, 1, __bf16>", "conv_mfma_wgrad2_k<1, 2, 3, 2>"),
+    (32, 48, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<1, 32, 1, 1, __bf16>", "conv_mfma_halo_k<32, 5, 0, __bf16>", "conv_mfma_wgrad2_k<1, 2, 3, 1>"),
+    # the few-channel layers: 8 padded channels per tap, and fp32
+    (8, 8, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_thin16_k<8, 1>", "conv_thin16_k<8, 1>", "conv_thin16_wgrad_k<8, 1>"),
+    (8, 32, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_thin16_k<8, 2>", "conv_mfma_halo2_k<1, 32, 1, 1, __bf16>", "conv_thin16_wgrad_k<8, 2>"),
+    (16, 16, 3, 1, False, (4, 8, 32), torch.float32, "conv_thin16f_k<16, 1>", "conv_thin16f_k<16, 1>", "conv_thin16f_wgrad_k<16, 1>"),
+    # small-grid stride-2 layers (the planned weight-gradient kernel, 32-channel gather blocks) and the 8-wide grids.  (The
+    # library splits the K loop of the last two and merges through gather_finalize_k, but the tag is the same with and
+    # without the split: these rows pin the gather variant only.)
+    (64, 128, 3, 2, False, (8, 8, 16), torch.bfloat16, "conv_mfma_gather_k<128, 0, __bf16>", "conv_mfma_gather_k<64, 1, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
+    (32, 32, 3, 2, False, (8, 8, 16), torch.bfloat16, "conv_mfma_gather_k<32, 0, __bf16>", "conv_mfma_gather_k<32, 1, __bf16>", "conv_mfma_wgrad_k<1, 1, 0, 1>"),
+    (128, 128, 3, 1, False, (4, 4, 8), torch.bfloat16, "conv_mfma_gather_k<128, 0, __bf16>", "conv_mfma_gather_k<128, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
+    (128, 128, 3, 1, False, (4, 4, 8), torch.float32, "conv_mfma_gather_k<128, 0, float>", "conv_mfma_gather_k<128, 0, float>", "conv_f32_wgrad_k<0, 7>"),
 ]
 
 
