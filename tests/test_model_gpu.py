@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+import _step_state as ss      # the per-tensor comparison of the step-state tests
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -402,6 +404,7 @@ def test_side_stream_weight_preparation_equals_one_stream():
             if mode != "one-stream":
                 assert len(ops.SidePrep._bufs) > 40
             res[mode] = (losses, opt.flat_g.clone(), opt.flat_p.clone())
+            layout = ss.flat_layout(gm, opt)
     finally:
         ops.SidePrep.enabled = was
     ref_l, ref_g, ref_p = res["one-stream"]
@@ -411,6 +414,9 @@ def test_side_stream_weight_preparation_equals_one_stream():
         for a in l:
             assert abs(a - ref_l[0]) <= 1e-5 * abs(ref_l[0]), (mode, l, ref_l)
         assert rel(g, ref_g) < 5e-3 and torch.equal(p_, ref_p), (mode, rel(g, ref_g))      # (norm / loss reductions use fp32 atomics)
+        # tensor by tensor (a norm over the whole buffer does not see a small tensor that is entirely wrong)
+        bad = ss.compare("fp32-direct", ss.flat_slices(layout, g), ss.flat_slices(layout, ref_g))
+        assert not bad, (mode, bad[:10])
 
 
 def test_side_stream_weight_gradients_equal_one_stream():
@@ -461,6 +467,7 @@ def test_side_stream_weight_gradients_equal_one_stream():
             used = ops.WgradSide.launched - n0
             assert (used == 0) if mode == "one-stream" else (used >= 40), (mode, used)
             res[mode] = (losses, g, opt.flat_p.clone())
+            layout = ss.flat_layout(gm, opt)
     finally:
         ops.WgradSide.enabled = was
     ref_l, ref_g, ref_p = res["one-stream"]
@@ -470,6 +477,8 @@ def test_side_stream_weight_gradients_equal_one_stream():
         for a in l:
             assert abs(a - ref_l[0]) <= 1e-5 * abs(ref_l[0]), (mode, l, ref_l)
         assert rel(g, ref_g) < 5e-3 and torch.equal(p_, ref_p), (mode, rel(g, ref_g))      # (norm / loss reductions use fp32 atomics)
+        bad = ss.compare("fp32-direct", ss.flat_slices(layout, g), ss.flat_slices(layout, ref_g))      # tensor by tensor
+        assert not bad, (mode, bad[:10])
 
 
 def test_weight_preparation_ahead_equals_inline():
@@ -509,6 +518,7 @@ def test_weight_preparation_ahead_equals_inline():
             used = ops.PrepAhead.used - n0
             assert (used == 0) if mode == "inline" else (used >= 60), (mode, used)
             res[mode] = (losses, opt.flat_g.clone(), opt.flat_p.clone())
+            layout = ss.flat_layout(gm, opt)
             if mode == "ahead":
                 # a second forward before the backward of the first: the persistent buffers are still needed -> in-line
                 opt.zero_grad()
@@ -531,6 +541,8 @@ def test_weight_preparation_ahead_equals_inline():
         for a in l:
             assert abs(a - ref_l[0]) <= 1e-5 * abs(ref_l[0]), (mode, l, ref_l)
         assert rel(g, ref_g) < 5e-3 and torch.equal(p_, ref_p), (mode, rel(g, ref_g))      # (norm / loss reductions use fp32 atomics)
+        bad = ss.compare("fp32-direct", ss.flat_slices(layout, g), ss.flat_slices(layout, ref_g))      # tensor by tensor
+        assert not bad, (mode, bad[:10])
 
 
 def _grad_scale(model):
