@@ -49,11 +49,20 @@ int conv_split_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* 
                      hipStream_t s, int accum);
 bool conv_split_wgrad2_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, hipStream_t s, int zeroed);
+// (algo 6, thin split: algo 5 plus the few-channel full-resolution layers, forward / data gradient and weight gradient)
+bool conv_split_thin_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+int conv_split_thin(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                    hipStream_t s, double2* stats, int stats_inst, int* stats_chunks);
+bool conv_split_thin_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+int conv_split_thin_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws, size_t ws_bytes,
+                          hipStream_t s, int zeroed);
 
-// the split kernel of a problem that resolved to 4: stride 1 under algo 4 and 5, the stride-2 families under algo 5 only
+// the split kernel of a problem that resolved to 4: stride 1 under algo 4, 5 and 6, the stride-2 families under algo 5 and 6,
+// the thin layers under algo 6 only (the three scopes are disjoint)
 static int split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
                      hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum) {
   if (conv_split_fwd_ok(d, x, y)) return conv_split_fwd(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
+  if (d->algo == 6 && conv_split_thin_ok(d, x, y)) return conv_split_thin(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
   return conv_split_tconv(d, x, wk, bias, y, s, accum);      // (statistics not fused: *stats_chunks stays 0, the caller runs the separate pass)
 }
 
@@ -62,6 +71,7 @@ extern "C" int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x
   if (conv_point1_ok(d, x, y)) return 1;            // one channel on a side: streaming dot / scale kernels (fp32 weights)
   if (d->algo == 4 && conv_split_fwd_ok(d, x, y)) return 4;   // split: the thick stride-1 3^3 fp32 layers; every other problem as algo 0
   if (d->algo == 5 && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y))) return 4;   // wide split: + stride-2 transposed / data gradient
+  if (d->algo == 6 && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y) || conv_split_thin_ok(d, x, y))) return 4;   // thin split: + C <= 16 at W >= 32
   if (conv_mfma_supported(d, x, y)) return 2;       // bf16 tensors: MFMA wherever the shape allows
   if (conv_f32mfma_supported(d, x, y)) return 3;    // fp32 tensors: fp32 MFMA wherever the shape allows
   return 1;
@@ -107,6 +117,7 @@ extern "C" int coma_conv_wgrad_algo(const coma_conv_desc* d, const coma_tensor* 
   if (d->algo == 1 || conv_point1_ok(d, x, dy)) return 1;
   if (d->algo == 4 && conv_split_wgrad_ok(d, x, dy)) return 4;
   if (d->algo == 5 && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy))) return 4;
+  if (d->algo == 6 && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy) || conv_split_thin_wgrad_ok(d, x, dy))) return 4;
   if (!conv_mfma_wgrad_supported(d, x, dy)) return 1;
   return x->dtype == COMA_BF16 ? 2 : 3;
 }
@@ -160,7 +171,11 @@ extern "C" int coma_conv_wgrad(const coma_conv_desc* d, const coma_tensor* x, co
   }
   if (conv_point1_ok(d, x, dy)) return conv_point1_wgrad(d, x, dy, dwk, s, zeroed);
   const int algo = coma_conv_wgrad_algo(d, x, dy);
-  if (algo == 4) return conv_split_wgrad_ok(d, x, dy) ? conv_split_wgrad(d, x, dy, dwk, s, zeroed) : conv_split_wgrad2(d, x, dy, dwk, s, zeroed);
+  if (algo == 4) {
+    if (conv_split_wgrad_ok(d, x, dy)) return conv_split_wgrad(d, x, dy, dwk, s, zeroed);
+    if (d->algo == 6 && conv_split_thin_wgrad_ok(d, x, dy)) return conv_split_thin_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);      // (merges into the replica scratch, as algo 0)
+    return conv_split_wgrad2(d, x, dy, dwk, s, zeroed);
+  }
   if (algo >= 2) return conv_mfma_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   return conv_direct_wgrad(d, x, dy, dwk, s, zeroed);
 }

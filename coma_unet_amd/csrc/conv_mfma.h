@@ -55,6 +55,9 @@ int conv_mfma_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_te
 bool conv_f32_halo2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+// the fp32 problems of conv_thin16f_k / conv_thin16f_wgrad_k
+bool conv_f32_thin_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+bool conv_f32_thin_wgrad_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 
 // ---- between conv_mfma.hip and conv_wgrad.hip only ----
 // Small weight tensors (the 1..16-channel layers, 1x1x1 gates): a thousand blocks merging into a few cache lines

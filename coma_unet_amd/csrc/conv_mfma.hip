@@ -3929,3 +3929,12 @@ bool conv_f32_tconv_problem(const coma_conv_desc* d, const coma_tensor* x, const
 bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   return d->stride == 2 && x->dtype == COMA_F32 && conv_mfma_wgrad_supported(d, x, dy) && !thin16f_wgrad_ok(d, x, dy) && f32_wgrad16_ok(d, x, dy);
 }
+
+// the fp32 problems conv_mfma_fwd runs on conv_thin16f_k / conv_mfma_wgrad on conv_thin16f_wgrad_k: what conv_split.hip adds
+// under algo 6
+bool conv_f32_thin_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return thin16f_ok(d, x, y);
+}
+bool conv_f32_thin_wgrad_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  return thin16f_wgrad_ok(d, x, dy);
+}

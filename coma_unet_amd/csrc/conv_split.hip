@@ -1,5 +1,5 @@
 // Split-bf16 convolution kernels for gfx950: fp32 tensors and fp32 kernel-layout weights, products on
-// v_mfma_f32_32x32x16_bf16 (coma_conv_desc.algo = 4).
+// v_mfma_f32_32x32x16_bf16 (coma_conv_desc.algo = 4, 5, 6).
 //
 // Every fp32 operand a is split when it is STAGED into LDS (once per element, not once per use) into two bf16 values
 //     a_hi = bf16(a),   a_lo = bf16(a - float(a_hi))            (both round-to-nearest-even)
@@ -16,6 +16,9 @@
 //   conv_split_tconv_k  -- stride-2 3x3x3 transposed convolution / data gradient of the stride-2 convolutions
 //                          (the problems of conv_mfma_tconv_k<float, *>)
 //   conv_split_wgrad2_k -- stride-2 and transposed 3x3x3 weight gradient (the problems of conv_f32_wgrad16_k<2, *>)
+// and, under algo = 6 (thin split), the few-channel full-resolution families on v_mfma_f32_16x16x32_bf16:
+//   conv_split_thin_k       -- stride-1 3x3x3 forward / data gradient, C <= 16 (the problems of conv_thin16f_k)
+//   conv_split_thin_wgrad_k -- their weight gradient                           (the problems of conv_thin16f_wgrad_k)
 #include "conv_mfma.h"    // s4_t / lds_s4_t, aligned16, conv_f32_*_problem: the fp32 problems the exact kernels take
 
 // 4 fp32 (one 16-byte staging piece) -> 4 bf16 hi + 4 bf16 lo
@@ -826,4 +829,505 @@ int conv_split_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_
   COMA_CHECK(conv_split_wgrad2_ok(d, x, dy), "conv_split_wgrad2: problem not in the split kernel's scope");
   return d->form == 0 ? launch_split_wgrad<2, conv_split_wgrad2_k<0>>(d, x, dy, dwk, s, zeroed)
                       : launch_split_wgrad<2, conv_split_wgrad2_k<1>>(d, x, dy, dwk, s, zeroed);
+}
+
+// =====================================================================================
+// Thin split (algo = 6): the few-channel full-resolution layers (C <= 16 and N <= 16, or C <= 8 and N <= 32; W >= 32) -- the
+// problems of conv_thin16f_k / conv_thin16f_wgrad_k -- on v_mfma_f32_16x16x32_bf16.
+//
+// conv_split_thin_k<CP, NB> -- forward / data gradient (`flip`), the structure of conv_thin16_k: the taps packed along K
+// (K = 32 = 2 taps x 16 channels at CP = 16: 14 steps; 4 taps x 8 channels at CP = 8: 7 steps), 2 x 4 x 32-voxel tiles, four
+// voxel groups of 16 per wave, persistent blocks, two per CU; staging by buffer loads (zero fill outside the volume), the next
+// tile's pieces issued one per step inside the MFMA loop, channels that are not the tensor's masked before the split.
+// The halo is TWO planes (hi, lo), each [816 rows][CP bf16] with the bf16 kernel's unpadded 32- / 16-byte row pitch, so a
+// 16-lane group's 16-byte fragment reads cover consecutive rows (conflict-free); one interleaved [hi][lo] row of 64 bytes
+// would put the group's lanes 64 bytes apart (4-way).  The weights sit in LDS as hi / lo FRAGMENTS in lane order
+// ([step][block][64 lanes][16 bytes], 27 x 16 NB x CP x 4 bytes in all, the fp32 twin's byte count): one conflict-free 16-byte
+// read per step, block and plane, shared by the wave's four voxel groups; in registers they would be 2 x 56 VGPRs next to
+// 64 of voxel fragments and 52 of staging pieces.  Epilogue and fused statistics as conv_thin16f_k.
+// =====================================================================================
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+
+struct SplitThinP {
+  const float* x; int ldx; long sbx; int D, H, W, C;
+  float* y; int ldy; long sby; int N;
+  const float* w; long wsb;
+  const float* bias; int bsb;
+  int flip;
+  unsigned xbytes;
+  int ntx, nty, ntz, ids_total, ids_per_block;
+  int st16;            // output rows allow aligned 16-byte (4-channel) stores
+  double2* stats; int stats_inst;
+};
+
+template <int CP, int NB> struct SplitThinTile {
+  static constexpr int HV = 34 * 6 * 4;
+  static constexpr int TPM = 32 / CP, NM = (27 + TPM - 1) / TPM;      // taps per MFMA, MFMA steps per voxel group
+  static constexpr int PLANE = HV * CP * 2;                           // one halo plane (bytes)
+  static constexpr int WPLANE = NM * NB * 64 * 16;                    // one weight-fragment plane (bytes)
+  static constexpr int LDS = 2 * PLANE + 2 * WPLANE;
+};
+
+template <int CP, int NB>      // CP = padded input channels per tap (16 or 8), NB = 16-channel output blocks (1 or 2)
+__global__ __launch_bounds__(256, 2) void conv_split_thin_k(SplitThinP p) {
+  using T = SplitThinTile<CP, NB>;
+  constexpr int TX = 32, TY = 4, TZ = 2, HX = TX + 2, HY = TY + 2, HV = T::HV;
+  constexpr int TPM = T::TPM, NM = T::NM;
+  constexpr int P = CP * 2;                       // row pitch of a halo plane (bytes)
+  constexpr int PCH = CP / 4;                     // 16-byte fp32 pieces per halo row
+  constexpr int HP = HV * PCH, HIT = (HP + 255) / 256;
+  static_assert(HIT <= NM, "one staging piece per MFMA step");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Hh = smem;                                // [HV][CP] bf16 hi
+  char* Hl = smem + T::PLANE;                     //          lo
+  char* Wh = smem + 2 * T::PLANE;                 // [NM][NB][64][8] bf16 hi
+  char* Wl = Wh + T::WPLANE;                      //                 lo
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z;
+  const int lv = lane & 15, lg = lane >> 4;       // voxel within the group / k group (A, B) = row group (D)
+  const float* xb = p.x + (long)b * p.sbx;
+  const float* wb = p.w + (long)b * p.wsb;
+  float* yb = p.y + (long)b * p.sby;
+
+  // ---- weights -> LDS fragments: lane (n = lv, k group lg) of step m holds w[tap][nb * 16 + n][8 channels] of its tap ----
+  for (int e = tid; e < NM * NB * 512; e += 256) {
+    const int j = e & 7, ln = (e >> 3) & 63, nb = (e >> 9) % NB, m = (e >> 9) / NB;
+    const int flv = ln & 15, flg = ln >> 4;
+    const int tap = m * TPM + (CP == 16 ? flg >> 1 : flg), c = (CP == 16 ? 8 * (flg & 1) : 0) + j, n = nb * 16 + flv;
+    const int wt = p.flip ? 26 - tap : tap;
+    const bool ok = tap < 27 && n < p.N && c < p.C;
+    const float v = ok ? wb[((long)wt * p.N + n) * p.C + c] : 0.f;
+    const bf16_t h = static_cast<bf16_t>(v);
+    reinterpret_cast<bf16_t*>(Wh)[e] = h;
+    reinterpret_cast<bf16_t*>(Wl)[e] = static_cast<bf16_t>(v - static_cast<float>(h));
+  }
+  // ---- B-fragment bases: this wave's first voxel group, this lane's voxel, its tap in step m, its channel half ----
+  const int tsub = CP == 16 ? lg >> 1 : lg, cofs = CP == 16 ? 8 * (lg & 1) : 0;
+  const int gz = wid >> 1, gy0 = 2 * (wid & 1);
+  int abase[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    const int tap = m * TPM + tsub < 27 ? m * TPM + tsub : 0;       // (padding taps have zero weights: read tap 0)
+    const int kx = tap % 3, ky = (tap / 3) % 3, kz = tap / 9;
+    abase[m] = (((gz + kz) * HY + gy0 + ky) * HX + lv + kx) * P + cofs * 2;
+  }
+  const int wfrag = lane * 16;                    // + (m * NB + nb) * 1024
+  // ---- staging descriptors: piece = tid + 256 it -> halo row piece / PCH, 4-channel quarter piece % PCH (a per-thread
+  // constant); the piece's 8 bytes of either plane sit at piece * 8 ----
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.xbytes, 0x00020000);
+  constexpr unsigned OOB = 0x7fff0000u;
+  int h_pos[HIT];                                 // hz | hy << 8 | hx << 16
+  unsigned h_boff[HIT];
+#pragma unroll
+  for (int it = 0; it < HIT; ++it) {
+    const int piece = tid + 256 * it;
+    const int row = piece / PCH, ch = piece % PCH;
+    const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+    h_pos[it] = piece < HP ? (hz | (hy << 8) | (hx << 16)) : (255 | (255 << 8) | (4095 << 16));
+    h_boff[it] = (unsigned)((((hz * p.H + hy) * p.W + hx) * p.ldx + ch * 4) * 4);
+  }
+  const int nval = p.C - 4 * (tid % PCH);
+  const uint4 hmask = make_uint4(nval > 0 ? ~0u : 0u, nval > 1 ? ~0u : 0u, nval > 2 ? ~0u : 0u, nval > 3 ? ~0u : 0u);
+  uint4 hreg[HIT];
+  auto issue = [&](int it, int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rs) __attribute__((always_inline)) {
+    const bool ok = (unsigned)(z0 - 1 + (h_pos[it] & 255)) < (unsigned)p.D && (unsigned)(y0 - 1 + ((h_pos[it] >> 8) & 255)) < (unsigned)p.H &&
+                    (unsigned)(x0 - 1 + (h_pos[it] >> 16)) < (unsigned)p.W;
+    const unsigned org_b = (unsigned)((((long)((z0 - 1) * p.H + (y0 - 1)) * p.W + (x0 - 1)) * p.ldx) * 4);   // (mod 2^32: a valid piece's sum is its true offset)
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? org_b + h_boff[it] : OOB, 0, 0);
+    hreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+  };
+  // the split happens here: one conversion per staged element, one 8-byte store per piece and plane
+  auto store_halo = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int it = 0; it < HIT; ++it)
+      if (tid + 256 * it < HP) {
+        uint4 v = hreg[it];
+        v.x &= hmask.x; v.y &= hmask.y; v.z &= hmask.z; v.w &= hmask.w;
+        uint2 hi, lo;
+        split4(v, hi, lo);
+        *reinterpret_cast<uint2*>(Hh + (tid + 256 * it) * 8) = hi;
+        *reinterpret_cast<uint2*>(Hl + (tid + 256 * it) * 8) = lo;
+      }
+  };
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  const bool do_stats = p.stats != nullptr;
+  float st_s[NB][4], st_q[NB][4], bv[NB][4];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int n = nb * 16 + 4 * lg + j;
+      st_s[nb][j] = 0.f; st_q[nb][j] = 0.f;
+      bv[nb][j] = (p.bias && n < p.N) ? p.bias[b * p.bsb + n] : 0.f;
+    }
+  if (id < id_end) {
+#pragma unroll
+    for (int it = 0; it < HIT; ++it) issue(it, tiz * TZ, tiy * TY, tix * TX, rs_x);
+  }
+  while (id < id_end) {
+    const int x0 = tix * TX, y0 = tiy * TY, z0 = tiz * TZ;
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+    // nothing to prefetch after the last tile: a zero-range descriptor makes every piece read as zero (no branch in the loop)
+    const __amdgpu_buffer_rsrc_t rs_n = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, has_next ? p.xbytes : 0, 0x00020000);
+    __syncthreads();                       // the previous tile's fragment reads are done (first tile: the weight image is complete)
+    store_halo();
+    __syncthreads();
+    f32x4_t acc[4][NB];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[q][nb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    // fragments one step ahead: the four voxel groups' rows and the step's weights, hi and lo
+    uint4 xh[2][4], xl[2][4], wh[2][NB], wl[2][NB];
+    auto rd = [&](int m, int bf) __attribute__((always_inline)) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int off = abase[m] + ((q >> 1) * HX + (q & 1) * 16) * P;
+        xh[bf][q] = *reinterpret_cast<const uint4*>(Hh + off);
+        xl[bf][q] = *reinterpret_cast<const uint4*>(Hl + off);
+      }
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        wh[bf][nb] = *reinterpret_cast<const uint4*>(Wh + wfrag + (m * NB + nb) * 1024);
+        wl[bf][nb] = *reinterpret_cast<const uint4*>(Wl + wfrag + (m * NB + nb) * 1024);
+      }
+    };
+    rd(0, 0);
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      if (m + 1 < NM) rd(m + 1, (m + 1) & 1);
+      if (m < HIT) issue(m, ntiz * TZ, ntiy * TY, ntix * TX, rs_n);      // one staging piece of the next tile per step
+      __builtin_amdgcn_sched_barrier(0);
+      // lo x hi, hi x lo, hi x hi (small terms first); the 4 NB accumulators of a term are independent
+#pragma unroll
+      for (int term = 0; term < 3; ++term)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) {
+            const uint4& a = term == 0 ? wl[m & 1][nb] : wh[m & 1][nb];
+            const uint4& f = term == 1 ? xl[m & 1][q] : xh[m & 1][q];
+            acc[q][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&f),
+                                                                 acc[q][nb], 0, 0, 0);
+          }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // ---- epilogue: lane = voxel lv of group q, output channels nb * 16 + 4 lg + 0..3 ----
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int vz = z0 + gz, vy = y0 + gy0 + (q >> 1), vx = x0 + (q & 1) * 16 + lv;
+      const bool valid = vz < p.D && vy < p.H && vx < p.W;
+      float* vox = yb + ((long)(vz * p.H + vy) * p.W + vx) * p.ldy;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const int n = nb * 16 + 4 * lg;
+        if (n >= p.N) continue;
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[j] = acc[q][nb][j] + bv[nb][j];
+          if (do_stats) { const float r = valid ? o[j] : 0.f; st_s[nb][j] += r; st_q[nb][j] = fmaf(r, r, st_q[nb][j]); }
+        }
+        if (valid) {
+          if (p.st16 && n + 3 < p.N) *reinterpret_cast<float4*>(vox + n) = make_float4(o[0], o[1], o[2], o[3]);
+          else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (n + j < p.N) vox[n + j] = o[j];
+          }
+        }
+      }
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+  // ---- fused statistics (as conv_thin16f_k): the 16 voxel lanes of a row group -> wave -> block (LDS) -> record ----
+  if (do_stats) {
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);          // [4 waves][32 ch][2]
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float a = st_s[nb][j], c = st_q[nb][j];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+        if (lv == 0) { red[(wid * 32 + nb * 16 + 4 * lg + j) * 2] = a; red[(wid * 32 + nb * 16 + 4 * lg + j) * 2 + 1] = c; }
+      }
+    __syncthreads();
+    if (tid < NB * 16 && tid < p.N) {
+      double a = 0.0, c = 0.0;
+      for (int w = 0; w < 4; ++w) { a += (double)red[(w * 32 + tid) * 2]; c += (double)red[(w * 32 + tid) * 2 + 1]; }
+      const int g = p.stats_inst ? b : 0;
+      stat_add(p.stats, p.stats_inst ? p.stats_inst : 1, p.N, g, tid, a, c);
+    }
+  }
+}
+
+bool conv_split_thin_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  return conv_f32_thin_problem(d, x, y);
+}
+
+int conv_split_thin(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                    hipStream_t s, double2* stats, int stats_inst, int* stats_chunks) {
+  COMA_CHECK(conv_split_thin_ok(d, x, y), "conv_split_thin: problem not in the split kernel's scope");
+  SplitThinP q;
+  q.x = (const float*)x->data; q.ldx = (int)x->ld; q.sbx = x->sb; q.D = x->D; q.H = x->H; q.W = x->W; q.C = x->C;
+  q.y = (float*)y->data; q.ldy = (int)y->ld; q.sby = y->sb; q.N = y->C;
+  q.w = (const float*)wk; q.wsb = d->per_sample_w ? 27L * y->C * x->C : 0;
+  q.bias = bias; q.bsb = d->per_sample_w ? y->C : 0;
+  q.flip = d->form == 1;
+  q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
+  q.st16 = y->ld % 4 == 0 && y->sb % 4 == 0 && aligned16(y->data);
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, x->B);      // two blocks per CU, one round
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
+  q.stats = nullptr; q.stats_inst = stats_inst;
+  if (stats) { q.stats = stats; *stats_chunks = 1; }
+  const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
+  const int cp = q.C > 8 ? 16 : 8, nb = q.N > 16 ? 2 : 1;      // (C <= 4 runs the CP = 8 variant)
+  coma_set_kernel_tag("conv_split_thin_k<%d, %d>", cp, nb);
+#define SPLIT_THIN(CP_, NB_) do { set_max_lds<conv_split_thin_k<CP_, NB_>, 80>(); \
+    hipLaunchKernelGGL((conv_split_thin_k<CP_, NB_>), grid, dim3(256), (size_t)(SplitThinTile<CP_, NB_>::LDS), s, q); } while (0)
+  if (cp == 16) SPLIT_THIN(16, 1);
+  else if (nb == 2) SPLIT_THIN(8, 2);
+  else SPLIT_THIN(8, 1);
+#undef SPLIT_THIN
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// =====================================================================================
+// conv_split_thin_wgrad_k<CP, NB> -- weight gradient of the same layers, the structure of conv_thin16_wgrad_k: the VOXELS
+// along K (32 per MFMA), rows = 16 output channels from the dense dy tile, columns = 16 = TPM taps x CP channels from the x
+// halo (27 column tiles at CP = 16, 14 at CP = 8), both operands voxel-major in LDS and read transposed with
+// ds_read_b64_tr_b16, all column tiles' accumulators stationary over the block's tiles.  Four images: x hi / lo
+// ([816 + 2][CP] bf16) and dy hi / lo ([256][16 NB] bf16), split once when staged.  Merge as the exact kernel: the four
+// waves add up in LDS, one fp32 atomic per weight into one of `nrep` replicas, wgrad_replica_sum behind the kernel.
+// CP = 16: 108 accumulator + 68 staging + 64 fragment registers: one block per CU (as conv_thin16f_wgrad_k<16, 1>); so is
+// <8, 2> (112 + 60 + 64: at two blocks per CU it spilled 55 registers).
+// =====================================================================================
+struct SplitThinWP {
+  const float* x; int ldx; long sbx; int D, H, W, C;
+  const float* dy; int ldn; long sbn; int N;
+  unsigned xbytes, dbytes;
+  int ntx, nty, ntz, ids_total, ids_per_block;
+  float* dwk; long wsb;
+  int nrep; long rep_stride;
+};
+
+template <int CP, int NB> struct SplitThinWTile {
+  static constexpr int HV = 34 * 6 * 4, TM = 256;
+  static constexpr int TPM = 16 / CP, NM = (27 + TPM - 1) / TPM;
+  static constexpr int XPL = (HV + 2) * CP * 2, DPL = TM * NB * 16 * 2;      // one x / dy plane (bytes)
+  static constexpr int IMG = 2 * XPL + 2 * DPL, RED = NM * NB * 256 * 4;
+  static constexpr int LDS = IMG > RED ? IMG : RED;
+};
+
+template <int CP, int NB>
+__global__ __launch_bounds__(256, CP == 16 || NB == 2 ? 1 : 2) void conv_split_thin_wgrad_k(SplitThinWP p) {
+  using T = SplitThinWTile<CP, NB>;
+  constexpr int TX = 32, TY = 4, TZ = 2, HX = TX + 2, HY = TY + 2, HV = T::HV, TM = T::TM;
+  constexpr int TPM = T::TPM, NM = T::NM;
+  constexpr int ND = NB * 16;                        // bf16 per dense dy row
+  constexpr int PX = CP * 2, PD = ND * 2;            // row pitches of a plane (bytes)
+  constexpr int PCH = CP / 4, DCH = ND / 4;          // 16-byte fp32 pieces per halo / dense row
+  constexpr int HP = HV * PCH, DP = TM * DCH, HIT = (HP + 255) / 256, DIT = DP / 256, NIT = HIT + DIT;
+  constexpr int RING = CP == 16 || NB == 2 ? 8 : 4;  // B fragment pairs in flight
+  constexpr int NPAIR = 2 * NM;
+  static_assert(NIT <= NPAIR, "one staging piece per MFMA step");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Xh = smem;                                   // [HV + 2][CP] bf16 hi
+  char* Xl = smem + T::XPL;                          //              lo
+  char* Dh = smem + 2 * T::XPL;                      // [TM][ND] bf16 hi
+  char* Dl = Dh + T::DPL;                            //               lo
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.z;
+  const int lv = lane & 15, lg = lane >> 4;
+  const float* xb = p.x + (long)b * p.sbx;
+  const float* db = p.dy + (long)b * p.sbn;
+  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.xbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(db), 0, p.dbytes, 0x00020000);
+  constexpr unsigned OOB = 0x7fff0000u;
+
+  // ---- staging descriptors: pieces 0..HIT-1 = x halo, HIT.. = dense dy; positions relative to the tile origin - 1, packed
+  // z | y << 4 | x << 8; a piece's 8 bytes of either plane sit at piece * 8 ----
+  int s_pos[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    if (it < HIT) {
+      const int row = (tid + 256 * it) / PCH;
+      const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
+      s_pos[it] = row < HV ? (hz | (hy << 4) | (hx << 8)) : (15 | (15 << 4) | (4095 << 8));
+    } else {
+      const int row = (tid + 256 * (it - HIT)) / DCH;
+      s_pos[it] = ((row >> 7) + 1) | ((((row >> 5) & 3) + 1) << 4) | (((row & 31) + 1) << 8);
+    }
+  }
+  const unsigned xoffb = (unsigned)((tid % PCH) * 16), doffb = (unsigned)((tid % DCH) * 16);
+  const int xval = p.C - 4 * (tid % PCH), dval = p.N - 4 * (tid % DCH);
+  const uint4 xmask = make_uint4(xval > 0 ? ~0u : 0u, xval > 1 ? ~0u : 0u, xval > 2 ? ~0u : 0u, xval > 3 ? ~0u : 0u);
+  const uint4 dmask = make_uint4(dval > 0 ? ~0u : 0u, dval > 1 ? ~0u : 0u, dval > 2 ? ~0u : 0u, dval > 3 ? ~0u : 0u);
+  uint4 sreg[NIT];
+  auto issue = [&](int it, int z0, int y0, int x0, const __amdgpu_buffer_rsrc_t& rx, const __amdgpu_buffer_rsrc_t& rd) __attribute__((always_inline)) {
+    const int gz = z0 - 1 + (s_pos[it] & 15), gy = y0 - 1 + ((s_pos[it] >> 4) & 15), gx = x0 - 1 + (s_pos[it] >> 8);
+    const bool ok = (unsigned)gz < (unsigned)p.D && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+    const unsigned off = (unsigned)(((gz * p.H + gy) * p.W + gx) * (it < HIT ? p.ldx : p.ldn)) * 4u + (it < HIT ? xoffb : doffb);
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(it < HIT ? rx : rd, ok ? off : OOB, 0, 0);
+    sreg[it] = make_uint4(v[0], v[1], v[2], v[3]);
+  };
+  auto store_tile = [&]() __attribute__((always_inline)) {      // the split: one conversion per staged element
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      uint4 v = sreg[it];
+      uint2 hi, lo;
+      if (it < HIT) {
+        v.x &= xmask.x; v.y &= xmask.y; v.z &= xmask.z; v.w &= xmask.w;
+        split4(v, hi, lo);
+        const int piece = tid + 256 * it;
+        if (piece < HP) { *reinterpret_cast<uint2*>(Xh + piece * 8) = hi; *reinterpret_cast<uint2*>(Xl + piece * 8) = lo; }
+      } else {
+        v.x &= dmask.x; v.y &= dmask.y; v.z &= dmask.z; v.w &= dmask.w;
+        split4(v, hi, lo);
+        const int piece = tid + 256 * (it - HIT);
+        *reinterpret_cast<uint2*>(Dh + piece * 8) = hi; *reinterpret_cast<uint2*>(Dl + piece * 8) = lo;
+      }
+    }
+  };
+
+  // ---- transposed-read addressing (as conv_thin16_wgrad_k): lane 4q+p of group lg supplies voxel x = 4 lg + q (+16 for the
+  // second read), columns 4p.. ----
+  const int gz = wid >> 1, gy0 = 2 * (wid & 1);
+  const int q4 = lv >> 2, p4 = lv & 3;
+  const int vx = 4 * lg + q4;
+  const int d_addr = ((gz * 4 + gy0) * 32 + vx) * PD + 8 * p4;                                   // + row step s * 32 * PD, + 16 * PD second read, + nb * 32 bytes
+  const int sub = (4 * p4) / CP, cin = (4 * p4) % CP;
+  const int x_addr = ((gz * HY + gy0) * HX + vx) * PX + cin * 2;                                 // + s * HX * PX, + 16 * PX second read, + tap offset
+  int toff[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    const int t = TPM == 1 ? m : (m * TPM + sub < 27 ? m * TPM + sub : 0);    // (padding taps read tap 0: their columns are never stored)
+    toff[m] = (((t / 9) * HY + (t / 3) % 3) * HX + t % 3) * PX;
+  }
+  f32x4_t acc[NM][NB];
+#pragma unroll
+  for (int m = 0; m < NM; ++m)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) acc[m][nb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
+  int id_end = id_begin + p.ids_per_block;
+  if (id_end > p.ids_total) id_end = p.ids_total;
+  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
+  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
+  if (id < id_end) {
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) issue(it, tiz * TZ, tiy * TY, tix * TX, rs_x, rs_d);
+  }
+  while (id < id_end) {
+    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
+    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
+    const bool has_next = nid < id_end;
+    const __amdgpu_buffer_rsrc_t rn_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, has_next ? p.xbytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(db), 0, has_next ? p.dbytes : 0, 0x00020000);
+    __syncthreads();
+    store_tile();
+    __syncthreads();
+    // the sequence of (row step s, column tile m) pairs is unrolled; B fragments (hi and lo) run RING pairs ahead
+    auto frag = [&](const char* src, int step) __attribute__((always_inline)) -> bf16x8_t {
+      const s4_t u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(src));
+      const s4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(src + step));
+      return (bf16x8_t){u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+    };
+    bf16x8_t bh[RING], bl[RING], ah[2][NB], al[2][NB];
+#pragma unroll
+    for (int s_ = 0; s_ < 2; ++s_)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        ah[s_][nb] = frag(Dh + d_addr + s_ * 32 * PD + nb * 32, 16 * PD);
+        al[s_][nb] = frag(Dl + d_addr + s_ * 32 * PD + nb * 32, 16 * PD);
+      }
+#pragma unroll
+    for (int pi = 0; pi < RING && pi < NPAIR; ++pi) {
+      const int xo = x_addr + (pi / NM) * HX * PX + toff[pi % NM];
+      bh[pi] = frag(Xh + xo, 16 * PX); bl[pi] = frag(Xl + xo, 16 * PX);
+    }
+#pragma unroll
+    for (int pi = 0; pi < NPAIR; ++pi) {
+      const int s_ = pi / NM, m = pi % NM;
+      const bf16x8_t ch = bh[pi % RING], cl = bl[pi % RING];
+      if (pi + RING < NPAIR) {
+        const int xo = x_addr + ((pi + RING) / NM) * HX * PX + toff[(pi + RING) % NM];
+        bh[pi % RING] = frag(Xh + xo, 16 * PX); bl[pi % RING] = frag(Xl + xo, 16 * PX);
+      }
+      if (pi < NIT) issue(pi, ntiz * TZ, ntiy * TY, ntix * TX, rn_x, rn_d);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int term = 0; term < 3; ++term)      // lo x hi, hi x lo, hi x hi
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+          acc[m][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? al[s_][nb] : ah[s_][nb], term == 1 ? cl : ch, acc[m][nb], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
+  }
+  // ---- merge (as conv_thin16f_wgrad_k): the four waves' tiles add up in LDS, then one fp32 atomic per weight into this
+  // block's replica ----
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(smem);                     // [NM][NB][16 n][16 col]
+  for (int i = tid; i < NM * NB * 256; i += 256) red[i] = 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < NM; ++m)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) atomicAdd(&red[((m * NB + nb) * 16 + 4 * lg + j) * 16 + lv], acc[m][nb][j]);
+  __syncthreads();
+  float* wout = p.dwk + (long)b * p.wsb + (long)(blockIdx.x % (unsigned)p.nrep) * p.rep_stride;
+  for (int i = tid; i < NM * NB * 256; i += 256) {
+    const int col = i & 15, row = (i >> 4) & 15, nb = (i >> 8) % NB, m = i / (256 * NB);
+    const int tap = m * TPM + col / CP, c = col % CP, n = nb * 16 + row;
+    if (tap < 27 && n < p.N && c < p.C) atomicAdd(wout + ((long)tap * p.N + n) * p.C + c, red[i]);
+  }
+}
+
+bool conv_split_thin_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
+  return conv_f32_thin_wgrad_problem(d, x, dy);
+}
+
+int conv_split_thin_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws, size_t ws_bytes,
+                          hipStream_t s, int zeroed) {
+  COMA_CHECK(conv_split_thin_wgrad_ok(d, x, dy), "conv_split_thin_wgrad: problem not in the split kernel's scope");
+  SplitThinWP q;
+  q.x = (const float*)x->data; q.ldx = (int)x->ld; q.sbx = x->sb; q.D = x->D; q.H = x->H; q.W = x->W; q.C = x->C;
+  q.dy = (const float*)dy->data; q.ldn = (int)dy->ld; q.sbn = dy->sb; q.N = dy->C;
+  q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * 4);
+  q.dbytes = (unsigned)((unsigned long long)t_vox(dy) * dy->ld * 4);
+  const int cp = q.C > 8 ? 16 : 8, nb = q.N > 16 ? 2 : 1;
+  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, cp == 16 || nb == 2 ? 256 : 512, x->B);      // <16, 1>, <8, 2>: one block per CU
+  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
+  const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
+  q.wsb = d->per_sample_w ? wsz1 : 0;
+  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
+  q.nrep = replicas ? WGRAD_NREP : 1;
+  q.rep_stride = replicas ? wsz : 0;
+  q.dwk = replicas ? (float*)ws : dwk;
+  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(q.dwk, 0, sizeof(float) * wsz * q.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
+  coma_set_kernel_tag("conv_split_thin_wgrad_k<%d, %d>", cp, nb);
+#define SPLIT_THINW(CP_, NB_) do { set_max_lds<conv_split_thin_wgrad_k<CP_, NB_>, 80>(); \
+    hipLaunchKernelGGL((conv_split_thin_wgrad_k<CP_, NB_>), grid, dim3(256), (size_t)(SplitThinWTile<CP_, NB_>::LDS), s, q); } while (0)
+  if (cp == 16) SPLIT_THINW(16, 1);
+  else if (nb == 2) SPLIT_THINW(8, 2);
+  else SPLIT_THINW(8, 1);
+#undef SPLIT_THINW
+  COMA_LAUNCH_CHECK();
+  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
 }

@@ -103,7 +103,15 @@ typedef struct coma_conv_desc {
                              weight gradients.  coma_conv_pick_algo / coma_conv_wgrad_algo answer 4 there too (the host's
                              weight preparation is the same: fp32 kernel-layout weights); coma_conv_accumulate_ok and
                              coma_conv_fwd_ws_bytes answer what they answer under algo 0.  Every other problem, and bf16
-                             tensors, resolve exactly as algo 0 does. */
+                             tensors, resolve exactly as algo 0 does.
+                             6 thin split: everything algo 5 resolves to the split kernels, plus the few-channel stride-1
+                             3x3x3 layers at W >= 32 on fp32 tensors (C <= 16 and N <= 16, or C <= 8 and N <= 32: forward,
+                             data gradient and weight gradient, per-sample or shared weights, fused statistics kept) on
+                             v_mfma_f32_16x16x32_bf16 with the same two-term split.  coma_conv_pick_algo /
+                             coma_conv_wgrad_algo answer 4 there too (fp32 kernel-layout weights); coma_conv_accumulate_ok,
+                             coma_conv_fwd_ws_bytes and coma_conv_wgrad_ws_bytes answer what they answer under algo 0 (the
+                             weight gradient merges into the same replica scratch and honours COMA_ZEROED_WS).  Every other
+                             problem, and bf16 tensors, resolve exactly as algo 0 does. */
 } coma_conv_desc;
 
 int         coma_abi_version(void);
@@ -146,7 +154,7 @@ int coma_routing_bwd(const float* cov, int32_t B, int32_t NC, const float* r, in
 
 /* ---- convolution (nn.Conv3d / nn.ConvTranspose3d and their data-gradients) ---- */
 /* which kernel family d->algo resolves to for this problem: 1 direct (wants fp32 wk), 2 bf16 MFMA
- * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk), 4 split-bf16 MFMA (algo 4 and 5 only; fp32
+ * (wants bf16 wk), 3 fp32 MFMA (fp32 tensors, wants fp32 wk), 4 split-bf16 MFMA (algo 4, 5 and 6 only; fp32
  * tensors, wants fp32 wk: the split is done inside the library).  The host prepares the kernel-layout
  * weights accordingly.  coma_conv_wgrad_algo answers the same question for the weight gradient.   */
 int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
