@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COMA_UNET_LIB") or os.path.join(_HERE, "libcoma_unet.so")   # (override: diagnostic builds, profiles/stamps_halo2.py)
 
 F32, BF16 = 0, 1
-ZEROED_OUT, ZEROED_WS, ACCUMULATE = 1, 2, 4
+ZEROED_OUT, ZEROED_WS, ACCUMULATE, WK_FRAG = 1, 2, 4, 8
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_SIGMOID, ACT_PRELU_RELU = range(6)
 NORM_BATCH, NORM_INSTANCE = 0, 1
 
@@ -29,6 +29,17 @@ class ConvDesc(C.Structure):
                 ("per_sample_w", C.c_int32), ("algo", C.c_int32)]
 
 
+class WprepItem(C.Structure):
+    _fields_ = [("master", C.c_void_p), ("r", C.c_void_p), ("E", C.c_int32), ("Bw", C.c_int32), ("A", C.c_int32),
+                ("B", C.c_int32), ("taps", C.c_int32), ("transposed", C.c_int32), ("out", C.c_void_p * 3),
+                ("dtype", C.c_int32 * 3), ("frag", C.c_int32)]
+
+
+class RoutingItem(C.Structure):
+    _fields_ = [("cov", C.c_void_p), ("Wr", C.c_void_p), ("br", C.c_void_p), ("bias_e", C.c_void_p), ("r", C.c_void_p),
+                ("bias_mix", C.c_void_p), ("B", C.c_int32), ("NC", C.c_int32), ("E", C.c_int32), ("N", C.c_int32)]
+
+
 _TP = C.POINTER(Tensor)
 _DP = C.POINTER(ConvDesc)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -41,12 +52,15 @@ SIGNATURES = {
     "coma_weight_prep": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _i32, _vp]),
     "coma_weight_prep_pair": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     "coma_weight_prep_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i32, _vp]),
+    "coma_weight_prep_batch": (_i32, [C.POINTER(WprepItem), _i32, _vp]),
+    "coma_routing_fwd_batch": (_i32, [C.POINTER(RoutingItem), _i32, _vp]),
     "coma_routing_fwd": (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "coma_routing_bwd": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "coma_conv_pick_algo": (_i32, [_DP, _TP, _TP]),
     "coma_conv_fwd": (_i32, [_DP, _TP, _vp, _i32, _vp, _TP, _vp]),
     "coma_conv_fwd_ws_bytes": (_sz, [_DP, _TP, _TP]),
     "coma_conv_accumulate_ok": (_i32, [_DP, _TP, _TP]),
+    "coma_conv_wk_frag_bytes": (_sz, [_DP, _TP, _TP]),
     "coma_conv_fwd_ws": (_i32, [_DP, _TP, _vp, _i32, _vp, _TP, _vp, _sz, _i32, _vp]),
     "coma_conv_fwd_norm_stats": (_i32, [_DP, _TP, _vp, _i32, _vp, _TP, _i32, _vp, _vp, _sz, _i32, _vp]),
     "coma_conv_wgrad_algo": (_i32, [_DP, _TP, _TP]),

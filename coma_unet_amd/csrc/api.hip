@@ -86,6 +86,11 @@ extern "C" size_t coma_conv_fwd_ws_bytes(const coma_conv_desc* d, const coma_ten
   return coma_conv_pick_algo(d, x, y) >= 2 ? conv_mfma_fwd_ws_bytes(d, x, y) : 0;
 }
 
+extern "C" size_t coma_conv_wk_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  if (!d || !x || !y) return 0;
+  return coma_conv_pick_algo(d, x, y) == 2 ? conv_mfma_wk_frag_bytes(d, x, y) : 0;
+}
+
 extern "C" int coma_conv_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, int32_t wk_dtype,
                              const float* bias, const coma_tensor* y, void* stream) {
   return coma_conv_fwd_ws(d, x, wk, wk_dtype, bias, y, nullptr, 0, 0, stream);
@@ -100,6 +105,10 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
   COMA_CHECK(!accum || coma_conv_accumulate_ok(d, x, y), "conv_fwd: COMA_ACCUMULATE is not supported for this problem (ask coma_conv_accumulate_ok)");
   hipStream_t s = (hipStream_t)stream;
   const int algo = coma_conv_pick_algo(d, x, y);
+  if (zeroed & COMA_WK_FRAG) {
+    COMA_CHECK(algo == 2 && wk_dtype == COMA_BF16 && !accum, "conv_fwd: COMA_WK_FRAG needs a bf16 MFMA problem (ask coma_conv_wk_frag_bytes)");
+    return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, nullptr, 0, 0, 0, 1);
+  }
   if (algo == 2) {
     COMA_CHECK(wk_dtype == COMA_BF16, "conv_fwd: MFMA path needs bf16 kernel-layout weights");
     COMA_CHECK(conv_mfma_supported(d, x, y), "conv_fwd: shape not supported by the MFMA path (C=%d N=%d dtype=%d)",
@@ -132,12 +141,14 @@ extern "C" int coma_conv_fwd_norm_stats(const coma_conv_desc* d, const coma_tens
   COMA_CHECK(wk && sums, "conv_fwd_norm_stats: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const int algo_ = coma_conv_pick_algo(d, x, y);
+  const int wk_frag = (zeroed & COMA_WK_FRAG) ? 1 : 0;
+  COMA_CHECK(!wk_frag || (algo_ == 2 && wk_dtype == COMA_BF16), "conv_fwd_norm_stats: COMA_WK_FRAG needs a bf16 MFMA problem (ask coma_conv_wk_frag_bytes)");
   if ((algo_ == 2 && wk_dtype == COMA_BF16) || (algo_ >= 3 && wk_dtype == COMA_F32)) {
     int fused = 0;
     const int inst = mode == COMA_NORM_INSTANCE ? y->B : 0;      // (the kernels' group count; 0 = one BatchNorm group)
     if (algo_ == 4) {
       if (int rc = split_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, 0)) return rc;
-    } else if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0)) return rc;
+    } else if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0, 0, wk_frag)) return rc;
     if (fused) return 0;
   } else {
     if (int rc = coma_conv_fwd(d, x, wk, wk_dtype, bias, y, stream)) return rc;

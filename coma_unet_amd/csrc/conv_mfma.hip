@@ -2581,12 +2581,23 @@ static size_t duo_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, cons
   return (size_t)(d->per_sample_w ? x->B : 1) * 27 * y->C * x->C * 2;
 }
 
+// does conv_mfma_halo<bf16_t> run this problem on conv_mfma_duo_k with fragment-ordered weights (given 16-byte aligned
+// weights)?  Every condition of the dispatch below that does not depend on the weight pointer or the scratch.
+static bool duo_wide_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  if (duo_frag_bytes(d, x, y) == 0 || x->C <= 32 || x->C % 32) return false;
+  const bool vecx = x->ld % 8 == 0 && x->sb % 8 == 0 && aligned16(x->data);
+  const bool st16 = y->ld % 8 == 0 && y->sb % 8 == 0 && aligned16(y->data);
+  return vecx && st16 && (unsigned long long)t_vox(x) * x->ld * sizeof(bf16_t) < 0x7fff0000ull &&
+         x->D <= 510 && x->H <= 510 && x->W <= 510;
+}
+
 // stats != NULL requests fused {sum, sumsq} partials; *stats_chunks receives the number of chunks written, or stays
 // 0 when the selected kernel variant cannot fuse them (the caller then runs the stand-alone statistics pass).
+// wk_frag: wk already holds duo_relayout_k's order (conv_mfma_wk_frag_bytes() > 0 was checked by the caller).
 template <typename T>
 static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias,
                           const coma_tensor* y, hipStream_t s, double2* stats = nullptr, int stats_inst = 0,
-                          int* stats_chunks = nullptr, void* ws = nullptr, size_t ws_bytes = 0) {
+                          int* stats_chunks = nullptr, void* ws = nullptr, size_t ws_bytes = 0, bool wk_frag = false) {
   constexpr int EPB = elem<T>::EPB;
   constexpr bool F32 = EPB == 4;
   HaloP p;
@@ -2658,10 +2669,12 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
       const bool no_duo = duo_mode() == 0, duo_all = duo_mode() == 2;
       q.wfrag = nullptr; q.wfrag_sb = 0;
       const size_t frag_bytes = duo_frag_bytes(d, x, y);      // C >= 64: scratch for the fragment-ordered copy of the weights
-      const bool wide_ok = duo_all && q.C > 32 && frag_bytes > 0 && ws && ws_bytes >= frag_bytes && aligned16(ws);
+      const bool wide_ok = duo_all && q.C > 32 && frag_bytes > 0 && (wk_frag || (ws && ws_bytes >= frag_bytes && aligned16(ws)));
       if (!no_duo && !thin && vec && (q.C == 32 || wide_ok) && q.N % 32 == 0 && q.st16 &&
           q.D <= 510 && q.H <= 510 && q.W <= 510) {
-        if (q.C > 32) {
+        if (q.C > 32 && wk_frag) {
+          q.wfrag = wk; q.wfrag_sb = d->per_sample_w ? 27L * q.N * q.C : 0;
+        } else if (q.C > 32) {
           const long pieces = (long)(frag_bytes / 16);
           hipLaunchKernelGGL(duo_relayout_k, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, (const uint4*)wk, (uint4*)ws, q.N, q.C / 8, pieces);
           COMA_LAUNCH_CHECK();
@@ -2687,6 +2700,7 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
         return 0;
       }
     }
+    COMA_CHECK(!wk_frag, "conv_mfma: fragment-ordered weights on a problem the wide two-group kernel does not take");
     if (lx == 5) {
     constexpr int HV2 = 34 * 6 * 4;
     const bool resident = thin || (!F32 && q.C == 32);
@@ -2739,6 +2753,13 @@ bool conv_mfma_accumulate_ok(const coma_conv_desc* d, const coma_tensor* x, cons
   return conv_mfma_supported(d, x, y) && !halo_ok(d, x, y);
 }
 
+// bytes of the kernel-layout weights in fragment order when this problem runs conv_mfma_duo_k on them (then the caller may
+// hand them over in that order -- wk_frag -- and the re-layout launch and its scratch go), else 0
+size_t conv_mfma_wk_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  if (x->dtype != COMA_BF16 || y->dtype != COMA_BF16 || !conv_mfma_supported(d, x, y) || !halo_ok(d, x, y) || !duo_wide_ok(d, x, y)) return 0;
+  return duo_frag_bytes(d, x, y);
+}
+
 size_t conv_mfma_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   if (x->dtype == COMA_F32) { if (thin16f_ok(d, x, y) || f32_halo_ok(d, x, y)) return 0; }
   else if (halo_ok(d, x, y)) return duo_frag_bytes(d, x, y);
@@ -2756,8 +2777,13 @@ size_t conv_mfma_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, con
 
 int conv_mfma_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias,
                   const coma_tensor* y, hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, void* ws,
-                  size_t ws_bytes, int ws_zeroed, int accum) {
+                  size_t ws_bytes, int ws_zeroed, int accum, int wk_frag) {
   const bool f32 = x->dtype == COMA_F32;
+  if (wk_frag) {
+    COMA_CHECK(!accum && aligned16(wk) && conv_mfma_wk_frag_bytes(d, x, y) > 0,
+               "conv_mfma: COMA_WK_FRAG on a problem the wide two-group kernel does not take (ask coma_conv_wk_frag_bytes)");
+    return conv_mfma_halo<bf16_t>(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks, nullptr, 0, true);
+  }
   COMA_CHECK(!accum || conv_mfma_accumulate_ok(d, x, y), "conv_mfma: this problem's kernel family cannot accumulate into y");
   if (f32 && thin16f_ok(d, x, y)) return conv_thin16f(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
   if (f32) { if (f32_halo_ok(d, x, y)) return conv_mfma_halo<float>(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks); }

@@ -148,7 +148,8 @@ def conv_plain(cfg, x, conv: nn.Module, ksize, stride, transposed, out=None, nor
     need_dx = x.requires_grad
     fdt, ddt = _wdtype(a_f), (_wdtype(a_d) if need_dx else None)
     pre = ops.PrepAhead.take(conv.weight, transposed, fdt, ddt)        # prepared at the start of this forward?
-    ops.PrepAhead.note(conv.weight, None, None, transposed, fdt, ddt)
+    ops.PrepAhead.note(conv.weight, None, None, transposed, fdt, ddt,
+                       ops.wk_frag(x.shape, x.dtype, n_out, ksize, stride, transposed, False, cfg.conv_algo))
     return ops.ConvLayer.apply(x, conv.weight, None, conv.bias if with_bias else None, ksize, stride, transposed, cfg.conv_algo,
                                Out(out) if out is not None else None, norm, fdt, ddt,
                                cfg.zero_bias_grad_under_norm, pre[2:] if pre is not None else None)
@@ -257,7 +258,8 @@ def conv_cond(cfg, x, cc: CondConv3d, covariate, out=None, norm=None):
     need_dx = x.requires_grad
     fdt, ddt = _wdtype(a_f), (_wdtype(a_d) if need_dx else None)
     pre = ops.PrepAhead.take(cc.weight, cc.is_transposed, fdt, ddt)    # routing + expert mix done at the start of this forward?
-    ops.PrepAhead.note(cc.weight, (cc.routing.weight, cc.routing.bias, cc.bias), cov.shape[1], cc.is_transposed, fdt, ddt)
+    ops.PrepAhead.note(cc.weight, (cc.routing.weight, cc.routing.bias, cc.bias), cov.shape[1], cc.is_transposed, fdt, ddt,
+                       ops.wk_frag(x.shape, x.dtype, cc.out_channels, cc.kernel_size, cc.stride, cc.is_transposed, True, cfg.conv_algo))
     r, bias = ops.Routing.apply(cov, cc.routing.weight, cc.routing.bias, cc.bias, pre[:2] if pre is not None else None)    # (B, E), (B, Cout)
     return ops.ConvLayer.apply(x, cc.weight, r, bias, cc.kernel_size, cc.stride, cc.is_transposed, cfg.conv_algo,
                                Out(out) if out is not None else None, norm, fdt, ddt,

@@ -389,10 +389,20 @@ class PrepAhead:
     them together, as parallel branches of the step graph under capture -- into persistent per-entry buffers, the main
     stream waits once, and the layers find their weights ready (`take`).  Any deviation from the recorded order, a second
     forward while a backward still needs the buffers, or COMA_PREP_AHEAD=0 falls back to the in-line preparation.
-    (Interleaved with the convolutions instead -- ops.SidePrep -- the same work on a second stream made the step SLOWER.)"""
+    (Interleaved with the convolutions instead -- ops.SidePrep -- the same work on a second stream made the step SLOWER.)
+    With `batch` (the default) the entries of a replayed plan are collected, not launched -- _prep_fwd appends an item while
+    begin() is collecting -- and flushed as ONE routing and ONE mix launch (coma_routing_fwd_batch, coma_weight_prep_batch) on the
+    first stream; the mix writes the weights of the wide two-group layers straight in fragment order (wk_frag, L.WK_FRAG)."""
     enabled = os.environ.get("COMA_PREP_AHEAD", "1") not in ("0", "")
     # streams: measured 17.70-17.85 ms per step without, 17.89 with 1, 17.53-17.56 with 2, 17.61 with 3, 17.85 with 4, 18.2 with 8
     K = int(os.environ.get("COMA_PREP_AHEAD_STREAMS", "2"))
+    # one batched routing launch and one batched mix launch per preparation stream instead of one to three launches per
+    # layer (coma_routing_fwd_batch / coma_weight_prep_batch: the per-layer launches are latency-bound, ~80 of them for
+    # ~0.15 ms of HBM traffic).  COMA_PREP_BATCH=0 restores the per-layer launches.
+    batch = os.environ.get("COMA_PREP_BATCH", "1") not in ("0", "")
+    batch_two_streams = os.environ.get("COMA_PREP_BATCH", "1") == "2"      # (A/B: plain re-layouts on a second stream)
+    _collect = None    # open collector of begin(): {stream handle: ([routing items], [mix items])}, keeps nothing else alive
+    _frag = 0          # fragment-order mask (bit 0: wk_f, bit 1: wk_d) of the entry begin() is handing to _prep_fwd
     _streams = {}
     _cur = None        # the running forward: {"mode", "plan", "i", "res", "owner", "key"}
     branch_streams = []  # preparation streams a model branch ran on in this step (the projection heads): joined with the side stream
@@ -436,10 +446,17 @@ class PrepAhead:
         # before the first layer runs)
         load = [0] * len(sts)
         res = [None] * len(plan)
+        if cls.batch:
+            cls._collect = {}
         for i in sorted(range(len(plan)), key=lambda j: -plan[j]["master"].numel()):
             e = plan[i]
-            k = load.index(min(load))
-            load[k] += e["master"].numel() + (1 << 18)          # (+ a launch's worth: the tiny layers are not free)
+            if cls.batch:
+                # batched: everything on the first stream (COMA_PREP_BATCH=2: the plain re-layouts beside the conditional
+                # layers on the second -- measured no faster, profiles/prep_batch_ab.txt)
+                k = min(1, len(sts) - 1) if cls.batch_two_streams and e["ncov"] is None else 0
+            else:
+                k = load.index(min(load))
+                load[k] += e["master"].numel() + (1 << 18)          # (+ a launch's worth: the tiny layers are not free)
             st = sts[k]
             with torch.cuda.stream(st):
                 master = e["master"]
@@ -450,8 +467,12 @@ class PrepAhead:
                     if e["bufs"] is None:
                         e["bufs"] = [_f32((batch, Wr.shape[0]), dev), _f32((batch, be.shape[1]), dev), None]
                     r, bm = e["bufs"][0], e["bufs"][1]
-                    check(lib.coma_routing_fwd(ptr(cov), batch, cov.shape[1], ptr(Wr), ptr(br), Wr.shape[0], ptr(be), be.shape[1],
-                                               ptr(r), ptr(bm), L.stream()), "coma_routing_fwd")
+                    if cls._collect is not None:
+                        cls._collect.setdefault(L.stream(), ([], []))[0].append(L.RoutingItem(
+                            ptr(cov), ptr(Wr), ptr(br), ptr(be), ptr(r), ptr(bm), batch, cov.shape[1], Wr.shape[0], be.shape[1]))
+                    else:
+                        check(lib.coma_routing_fwd(ptr(cov), batch, cov.shape[1], ptr(Wr), ptr(br), Wr.shape[0], ptr(be), be.shape[1],
+                                                   ptr(r), ptr(bm), L.stream()), "coma_routing_fwd")
                 elif e["bufs"] is None:
                     e["bufs"] = [None, None, None]
                 if e["bufs"][2] is None:
@@ -462,19 +483,36 @@ class PrepAhead:
                     Bw_ = batch if r is not None else 1
                     e["bufs"][2] = (_new((Bw_, taps_, cout_, cin_), e["fwd_dtype"], dev),
                                     _new((Bw_, taps_, cin_, cout_), e["dgrad_dtype"], dev) if e["dgrad_dtype"] is not None else None)
+                # which of the two the batched mix writes in fragment order -- what the library asked for in the recording
+                # forward (note); only the batched mix can: read by _prep_fwd while it appends this entry's item
+                cls._frag = e["frag"] if cls.batch else 0
                 wk_f, wk_d, rr, pmeta = _prep_fwd(master, r, e["transposed"], e["fwd_dtype"], e["dgrad_dtype"], e["bufs"][2])
+                cls._frag = 0
                 res[i] = (r, bm, wk_f, wk_d, rr, pmeta)
+        cls._flush()
         for st in sts:
             main.wait_stream(st)
         cls._cur = {"mode": "replay", "plan": plan, "i": 0, "res": res, "owner": owner, "key": key}
 
     @classmethod
-    def note(cls, master, routing, ncov, transposed, fwd_dtype, dgrad_dtype):
-        """Recording forward: this layer prepares `master` this way."""
+    def _flush(cls):
+        """Launch what begin() collected: per stream one batched routing launch, then one batched mix launch."""
+        col, cls._collect = cls._collect, None
+        for st, (routes, mixes) in (col or {}).items():
+            if routes:
+                check(lib.coma_routing_fwd_batch((L.RoutingItem * len(routes))(*routes), len(routes), st), "coma_routing_fwd_batch")
+            if mixes:
+                check(lib.coma_weight_prep_batch((L.WprepItem * len(mixes))(*mixes), len(mixes), st), "coma_weight_prep_batch")
+
+    @classmethod
+    def note(cls, master, routing, ncov, transposed, fwd_dtype, dgrad_dtype, frag=0):
+        """Recording forward: this layer prepares `master` this way.  frag: wk_frag() of the layer's forward and
+        data-gradient problems -- the directions whose kernel wants its weights in fragment order."""
         c = cls._cur
         if c is not None and c["mode"] == "record":
             c["plan"].append({"master": master, "routing": routing, "ncov": ncov, "transposed": bool(transposed),
-                              "fwd_dtype": fwd_dtype, "dgrad_dtype": dgrad_dtype, "bufs": None})
+                              "fwd_dtype": fwd_dtype, "dgrad_dtype": dgrad_dtype, "bufs": None,
+                              "frag": (frag & 1) | (frag & 2 if dgrad_dtype is not None else 0)})
 
     @classmethod
     def take(cls, master, transposed, fwd_dtype, dgrad_dtype):
@@ -573,12 +611,24 @@ def _prep_fwd(master, r, transposed, fwd_dtype, dgrad_dtype, bufs=None):
     Bw = r.shape[0] if has_e else 1
     rr = r.contiguous().float() if has_e else None
     dev = master.device
+    frag = 0
     if bufs is not None:
         wk_f, wk_d = bufs
+        frag = PrepAhead._frag if PrepAhead._collect is not None else 0
     else:
         wk_f = _new((Bw, taps, cout, cin), fwd_dtype, dev)
         wk_d = _new((Bw, taps, cin, cout), dgrad_dtype, dev) if dgrad_dtype is not None else None
-    if taps == 27:
+    if bufs is not None and PrepAhead._collect is not None and taps in (1, 27):
+        # PrepAhead.begin is collecting: this layer becomes one item of the forward's batched mix launch
+        ab, ba = (wk_d, wk_f) if transposed else (wk_f, wk_d)
+        it = L.WprepItem(ptr(m), ptr(rr), E, Bw, A, Bc, taps, int(bool(transposed)))
+        for k, o in enumerate((ab, ba)):
+            if o is not None:
+                it.out[k], it.dtype[k] = ptr(o), L.dtype_code(o.dtype)
+        if frag:      # (bit 0: wk_f, bit 1: wk_d) -> (bit 0: ab, bit 1: ba)
+            it.frag = ((frag & 1) << 1 | (frag & 2) >> 1) if transposed else frag
+        PrepAhead._collect.setdefault(L.stream(), ([], []))[1].append(it)
+    elif taps == 27:
         # one pass over the experts writes both layouts: [tap][A][B] and [tap][B][A] of master [E][A][B][27]
         ab, ba = (wk_d, wk_f) if transposed else (wk_f, wk_d)
         check(lib.coma_weight_prep_pair(ptr(m), ptr(rr), E, Bw, A, Bc, ptr(ab), L.dtype_code(ab.dtype) if ab is not None else 0,
@@ -590,12 +640,13 @@ def _prep_fwd(master, r, transposed, fwd_dtype, dgrad_dtype, bufs=None):
         if wk_d is not None:
             check(lib.coma_weight_prep(ptr(m), ptr(rr), E, Bw, cin, cout, taps, se, sc_f, sn_f, ptr(wk_d),
                                        L.dtype_code(dgrad_dtype), L.stream()), "coma_weight_prep")
-    return wk_f, wk_d, rr, (has_e, E, Bw, cout, cin, taps, se, sn_f, sc_f)
+    # (a tenth element: the fragment-order mask of (wk_f, wk_d), only when one of them is in that order)
+    return wk_f, wk_d, rr, (has_e, E, Bw, cout, cin, taps, se, sn_f, sc_f) + ((frag,) if frag else ())
 
 
 def _prep_bwd(dwk, master, rr, meta, p_master):
     """fp32 dwk [Bw, taps, Cout, Cin] -> (dmaster or None when written through to p_master.grad, dr or None)."""
-    has_e, E, Bw, cout, cin, taps, se, sn_f, sc_f = meta
+    has_e, E, Bw, cout, cin, taps, se, sn_f, sc_f = meta[:9]
     sink = GradSink.slot(p_master)
     dmaster = sink if sink is not None else torch.empty_like(master)
     dr, zeroed = None, 0
@@ -717,6 +768,18 @@ def pick_algo(x_shape, x_dtype, n_out, ksize, stride, transposed, per_sample, de
     return a_f, a_d
 
 
+def wk_frag(x_shape, x_dtype, n_out, ksize, stride, transposed, per_sample, algo=0):
+    """Which of a layer's two convolution problems want their kernel-layout weights in fragment order
+    (coma_conv_wk_frag_bytes on contiguous tensors of these shapes): bit 0 the forward, bit 1 the data gradient."""
+    B, Do, Ho, Wo = conv_out_grid(x_shape, ksize, stride, transposed)
+    xt = L.Tensor(None, L.dtype_code(x_dtype), x_shape[0], x_shape[1], x_shape[2], x_shape[3], x_shape[4], x_shape[4], 0)
+    yt = L.Tensor(None, L.dtype_code(x_dtype), B, Do, Ho, Wo, n_out, n_out, 0)
+    form = 1 if transposed else 0
+    f = lib.coma_conv_wk_frag_bytes(_desc(ksize, stride, form, per_sample, algo), xt, yt) > 0
+    d = lib.coma_conv_wk_frag_bytes(_desc(ksize, stride, 1 - form, per_sample, algo), yt, xt) > 0
+    return int(f) | int(d) << 1
+
+
 def _scratch(nbytes, device, lane=0):
     """(buffer, zeroed flag): the convolution's scratch as a private zeroed arena slice when the step's arena is armed
     (the library then skips its memset), else the shared stream-ordered workspace (of the side stream: lane 1)."""
@@ -727,10 +790,10 @@ def _scratch(nbytes, device, lane=0):
     return workspace(nbytes, device, lane), 0
 
 
-def _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm):
+def _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm, frag=False):
     """One forward launch; with `norm` (the mode of the normalisation that follows: L.NORM_BATCH / L.NORM_INSTANCE, or a
     tuple starting with it) its fp64 statistics record sums[G, C, 2] = {sum, sumsq} comes out of the same pass:
-    returns (y, sums) then, else (y, None)."""
+    returns (y, sums) then, else (y, None).  frag: wk_f holds fragment order (L.WK_FRAG: no re-layout, no scratch)."""
     B, Do, Ho, Wo = conv_out_grid(x.shape, ksize, stride, form == 1)
     n = wk_f.shape[2]
     y = out.t if out is not None else _new((B, Do, Ho, Wo, n), x.dtype, x.device)
@@ -739,7 +802,10 @@ def _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm):
     tag = (tuple(x.shape), n, ksize, stride, form)
     cx, cy = ct(x), ct(y)
     kind = conv_class(_ALGO_NAMES[lib.coma_conv_pick_algo(d, cx, cy)] if KernelTimer.enabled else "", x.shape[4], n)
-    ws, zf = _scratch(lib.coma_conv_fwd_ws_bytes(d, cx, cy), x.device)      # split-K scratch of the deep layers
+    if frag:
+        ws, zf = workspace(0, x.device), L.WK_FRAG
+    else:
+        ws, zf = _scratch(lib.coma_conv_fwd_ws_bytes(d, cx, cy), x.device)      # split-K scratch of the deep layers
     if norm is None:
         KernelTimer.run("conv_fwd", kind, conv_flops(x.shape, y.shape, ksize, stride),
                         lambda: check(lib.coma_conv_fwd_ws(d, cx, ptr(wk_f), L.dtype_code(wk_f.dtype), ptr(b), cy, ptr(ws),
@@ -756,7 +822,7 @@ def _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm):
 
 
 def _conv_bwd(x, wk_d, dy, ksize, stride, form, per_sample, algo, wshape, need_dx, need_dw, bias_mode, p_bias, fork=None,
-              side=False):
+              side=False, frag=False):
     """-> dx, dwk (fp32, kernel layout), dbias (None when absent, written through, or identically zero).
     bias_mode: 0 no bias, 1 reduce dy over the voxels, 2 the bias feeds a mean-removing normalisation (its gradient is
     identically zero: exact zeros are returned instead of a reduction of rounding noise).
@@ -784,7 +850,10 @@ def _conv_bwd(x, wk_d, dy, ksize, stride, form, per_sample, algo, wshape, need_d
         else:
             dx = _new(x.shape, x.dtype, x.device)
         cdx = ct(dx)
-        wsd, zfd = _scratch(lib.coma_conv_fwd_ws_bytes(dd, cdy_, cdx), x.device)
+        if frag:      # wk_d holds fragment order (L.WK_FRAG: no re-layout, no scratch)
+            wsd, zfd = workspace(0, x.device), L.WK_FRAG
+        else:
+            wsd, zfd = _scratch(lib.coma_conv_fwd_ws_bytes(dd, cdy_, cdx), x.device)
         KernelTimer.run("conv_dgrad", conv_class(_ALGO_NAMES[lib.coma_conv_pick_algo(dd, cdy_, cdx)] if KernelTimer.enabled else "",
                                                    dy.shape[4], x.shape[4]),
                         conv_flops(dy.shape, dx.shape, ksize, stride),
@@ -894,7 +963,8 @@ class ConvLayer(Function):
             if SidePrep._on:
                 SidePrep.fence(x.device)      # (routing / bias mix of this layer were queued on the side stream)
             wk_f, wk_d, rr, pmeta = _prep_fwd(master, r, transposed, fwd_dtype, dgrad_dtype)
-        y, sums = _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm)
+        frag = pmeta[9] if len(pmeta) > 9 else 0
+        y, sums = _conv_fwd(x, wk_f, bias, ksize, stride, form, per_sample, algo, out, norm, **({"frag": True} if frag & 1 else {}))
         ctx.save_for_backward(x, wk_d, master, rr)
         ctx.fork = getattr(x, "_coma_fork", None)
         ctx.side = bool(side)
@@ -927,7 +997,8 @@ class ConvLayer(Function):
         # follows onto the side stream
         wside = need_dw and WgradSide.usable(x.device, (ctx.p_master, ctx.p_bias if bias_mode else None))
         dx, dwk, dbias = _conv_bwd(x, wk_d, dy, ksize, stride, form, per_sample, algo, wshape, ctx.needs_input_grad[0],
-                                   need_dw, bias_mode, ctx.p_bias, ctx.fork, wside)
+                                   need_dw, bias_mode, ctx.p_bias, ctx.fork, wside,
+                                   **({"frag": True} if len(pmeta) > 9 and pmeta[9] & 2 else {}))
         dmaster = dr = None
         if ctx.side:
             SidePrep._live = max(0, SidePrep._live - 1)

@@ -23,6 +23,11 @@
  *  - No function allocates, synchronises or keeps global state.  `stream` is a
  *    hipStream_t passed as void*.  Return value 0 = ok, otherwise an error code;
  *    coma_last_error() returns a thread-local message.
+ *  - Process-wide switches, read once from the environment, all for A/B measurements
+ *    of one build: COMA_NO_DUO, COMA_DUO_C32_ONLY, COMA_NO_TCONV, COMA_THIN16 (kernel
+ *    dispatch of the convolutions), COMA_WPREP_BWD_OLD, COMA_WPREP_BWD_SPLIT (form of
+ *    the expert scatter).  The Python host has its own, among
+ *    them COMA_PREP_AHEAD and COMA_PREP_BATCH (batched weight preparation).
  *  - Workspaces are caller-provided; the *_ws_bytes query says how much.
  */
 #ifndef COMA_UNET_H
@@ -54,7 +59,11 @@ enum { COMA_ZEROED_OUT = 1, COMA_ZEROED_WS = 2,
        /* coma_conv_fwd_ws only: y += conv(x) instead of y = conv(x) -- a data gradient added to the gradient another
         * consumer of the same activation has already written (no separate accumulation pass); valid where
         * coma_conv_accumulate_ok() answers 1 (the gather / pointwise kernel families)                                */
-       COMA_ACCUMULATE = 4 };
+       COMA_ACCUMULATE = 4,
+       /* coma_conv_fwd_ws / coma_conv_fwd_norm_stats: `wk` is already in the fragment order of the wide two-group kernel
+        * (coma_weight_prep_batch wrote it so; layout: coma_conv_wk_frag_bytes) -- no re-layout launch, no scratch for it.
+        * Only where coma_conv_wk_frag_bytes() answers non-zero: any other problem returns an error and runs nothing. */
+       COMA_WK_FRAG = 8 };
 
 /* activation after a normalisation (MONAI ADN "A" slot) */
 enum {
@@ -140,12 +149,40 @@ int coma_weight_prep_bwd(const float* dwk, const float* master, const float* r, 
                          int32_t Bw, int32_t N, int32_t C, int32_t taps, int64_t se,
                          int64_t sn, int64_t sc, float* dmaster, float* dr, int32_t zeroed, void* stream);
 
+/* Every mix of a forward pass in one launch (per layer the mixes are launch- and latency-bound).  `items` is a HOST array,
+ * one item per layer, read during the call: the table travels by value in the kernel arguments (chunked into several
+ * launches beyond a few dozen items), so the device pointers are the ones valid at call time -- as with the per-layer entry
+ * points, also inside a captured graph.  master [E][A][B][taps] fp32, taps 27 or 1; r [Bw][E] or NULL (E = 1);
+ * out[0] [Bw][taps][A][B], out[1] [Bw][taps][B][A] (the two kernel layouts: forward and data gradient, which is which
+ * follows from `transposed`, informative here), each NULL or of dtype[i]; out[2] is reserved and must be NULL.  With bit i of
+ * `frag` set, out[i] takes the fragment order the wide two-group convolution kernel stages from instead (27 taps, bf16,
+ * 16-byte aligned, n % 32 == 0 and c % 16 == 0 for its [n][c] = [A][B] or [B][A]; layout: coma_conv_wk_frag_bytes): the
+ * same values, permuted.  The arithmetic per output element is that of coma_weight_prep_pair / coma_weight_prep: the
+ * results are bit-identical to the per-layer calls.                                                                 */
+typedef struct coma_wprep_item {
+  const float* master;
+  const float* r;
+  int32_t E, Bw, A, B, taps, transposed;
+  void*   out[3];
+  int32_t dtype[3];
+  int32_t frag;           /* bit i: out[i] (i < 2) is written in fragment order (see below) */
+} coma_wprep_item;
+int coma_weight_prep_batch(const coma_wprep_item* items /* host */, int32_t n, void* stream);
+
 /* ---- CondConv routing (call sites attn_unet_data_parallel.py:285-306):
  *      r[b][e] = sigmoid(cov[b] . Wr[e] + br[e]);  bias_mix[b][n] = sum_e r[b][e] * bias_e[e][n]
  * cov fp32 [B][NC], Wr [E][NC], br [E], bias_e [E][N] (or NULL with bias_mix NULL); B*E <= 64.   */
 int coma_routing_fwd(const float* cov, int32_t B, int32_t NC, const float* Wr, const float* br,
                      int32_t E, const float* bias_e, int32_t N, float* r, float* bias_mix,
                      void* stream);
+/* coma_routing_fwd for every conditional layer of a forward pass in one launch; `items`: HOST array (see
+ * coma_weight_prep_batch).  r and bias_mix are bit-identical to the per-layer call's.                           */
+typedef struct coma_routing_item {
+  const float* cov; const float* Wr; const float* br; const float* bias_e;
+  float* r; float* bias_mix;
+  int32_t B, NC, E, N;
+} coma_routing_item;
+int coma_routing_fwd_batch(const coma_routing_item* items /* host */, int32_t n, void* stream);
 /* dr_w [B][E] (gradient reaching r through the mixed weights, or NULL), dbias_mix [B][N] (or
  * NULL)  ->  dWr [E][NC], dbr [E], dbias_e [E][N] (or NULL); all written with "=".             */
 int coma_routing_bwd(const float* cov, int32_t B, int32_t NC, const float* r, int32_t E,
@@ -165,6 +202,11 @@ int coma_conv_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk,
  * ws_bytes >= coma_conv_fwd_ws_bytes(...) enables it; a smaller or NULL ws runs the unsplit kernel.          */
 size_t coma_conv_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 int coma_conv_accumulate_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+/* Non-zero (the size of the weights in bytes) when this problem runs on the wide two-group kernel, which stages its weights
+ * from FRAGMENT order: bf16 wk[b][n / 32][c / 16][tap][lane = (n & 31) + 32 * ((c >> 3) & 1)][c & 7] instead of
+ * wk[b][tap][n][c].  A caller that prepares them in that order passes COMA_WK_FRAG; with plain weights the library
+ * re-lays them into the workspace itself (coma_conv_fwd_ws_bytes).  0: the plain layout is wanted.                  */
+size_t coma_conv_wk_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, const void* wk, int32_t wk_dtype,
                      const float* bias, const coma_tensor* y, void* ws, size_t ws_bytes, int32_t zeroed, void* stream);
 /* conv forward + statistics of the BatchNorm(train)/InstanceNorm that follows it (MONAI Convolution =
