@@ -57,12 +57,18 @@ bool conv_split_thin_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, con
 int conv_split_thin_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws, size_t ws_bytes,
                           hipStream_t s, int zeroed);
 
-// the split kernel of a problem that resolved to 4: stride 1 under algo 4, 5 and 6, the stride-2 families under algo 5 and 6,
-// the thin layers under algo 6 only (the three scopes are disjoint)
+// (algo 7, pointwise: algo 6 plus the 1x1x1 fp32 layers with several channels on both sides on the exact fp32 MFMA:
+// conv_pw_f32.hip, declared in conv_mfma.h.  These problems resolve to 3 -- fp32 kernel-layout weights)
+static bool thin_on(const coma_conv_desc* d) { return d->algo == 6 || d->algo == 7; }
+static bool pw_fwd(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) { return d->algo == 7 && conv_pw_f32_ok(d, x, y); }
+static bool pw_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) { return d->algo == 7 && conv_pw_f32_wgrad_ok(d, x, dy); }
+
+// the split kernel of a problem that resolved to 4: stride 1 under algo 4 to 7, the stride-2 families under algo 5 to 7,
+// the thin layers under algo 6 and 7 only (the three scopes are disjoint)
 static int split_fwd(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
                      hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum) {
   if (conv_split_fwd_ok(d, x, y)) return conv_split_fwd(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
-  if (d->algo == 6 && conv_split_thin_ok(d, x, y)) return conv_split_thin(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
+  if (thin_on(d) && conv_split_thin_ok(d, x, y)) return conv_split_thin(d, x, wk, bias, y, s, stats, stats_inst, stats_chunks);
   return conv_split_tconv(d, x, wk, bias, y, s, accum);      // (statistics not fused: *stats_chunks stays 0, the caller runs the separate pass)
 }
 
@@ -71,7 +77,8 @@ extern "C" int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x
   if (conv_point1_ok(d, x, y)) return 1;            // one channel on a side: streaming dot / scale kernels (fp32 weights)
   if (d->algo == 4 && conv_split_fwd_ok(d, x, y)) return 4;   // split: the thick stride-1 3^3 fp32 layers; every other problem as algo 0
   if (d->algo == 5 && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y))) return 4;   // wide split: + stride-2 transposed / data gradient
-  if (d->algo == 6 && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y) || conv_split_thin_ok(d, x, y))) return 4;   // thin split: + C <= 16 at W >= 32
+  if (thin_on(d) && (conv_split_fwd_ok(d, x, y) || conv_split_tconv_ok(d, x, y) || conv_split_thin_ok(d, x, y))) return 4;   // thin split: + C <= 16 at W >= 32
+  if (pw_fwd(d, x, y)) return 3;                    // pointwise: the 1x1x1 fp32 layers on conv_pw_f32_k (ksize 1: none of the split scopes)
   if (conv_mfma_supported(d, x, y)) return 2;       // bf16 tensors: MFMA wherever the shape allows
   if (conv_f32mfma_supported(d, x, y)) return 3;    // fp32 tensors: fp32 MFMA wherever the shape allows
   return 1;
@@ -79,10 +86,12 @@ extern "C" int coma_conv_pick_algo(const coma_conv_desc* d, const coma_tensor* x
 
 extern "C" int coma_conv_accumulate_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   const int algo = coma_conv_pick_algo(d, x, y);
+  if (pw_fwd(d, x, y)) return 1;
   return algo >= 2 && conv_mfma_accumulate_ok(d, x, y) ? 1 : 0;
 }
 
 extern "C" size_t coma_conv_fwd_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
+  if (pw_fwd(d, x, y)) return 0;
   return coma_conv_pick_algo(d, x, y) >= 2 ? conv_mfma_fwd_ws_bytes(d, x, y) : 0;
 }
 
@@ -117,6 +126,7 @@ extern "C" int coma_conv_fwd_ws(const coma_conv_desc* d, const coma_tensor* x, c
   }
   COMA_CHECK(wk_dtype == COMA_F32, "conv_fwd: fp32 tensors need fp32 kernel-layout weights");
   if (algo == 4) return split_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, accum);
+  if (pw_fwd(d, x, y)) return conv_pw_f32(d, x, wk, bias, y, s, nullptr, 0, nullptr, accum);
   if (algo == 3) return conv_mfma_fwd(d, x, wk, bias, y, s, nullptr, 0, nullptr, ws, ws_bytes, wz, accum);
   if (conv_point1_ok(d, x, y)) return conv_point1_fwd(d, x, (const float*)wk, bias, y, s);
   return conv_direct_fwd(d, x, (const float*)wk, bias, y, s);
@@ -126,7 +136,8 @@ extern "C" int coma_conv_wgrad_algo(const coma_conv_desc* d, const coma_tensor* 
   if (d->algo == 1 || conv_point1_ok(d, x, dy)) return 1;
   if (d->algo == 4 && conv_split_wgrad_ok(d, x, dy)) return 4;
   if (d->algo == 5 && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy))) return 4;
-  if (d->algo == 6 && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy) || conv_split_thin_wgrad_ok(d, x, dy))) return 4;
+  if (thin_on(d) && (conv_split_wgrad_ok(d, x, dy) || conv_split_wgrad2_ok(d, x, dy) || conv_split_thin_wgrad_ok(d, x, dy))) return 4;
+  if (pw_wgrad(d, x, dy)) return 3;
   if (!conv_mfma_wgrad_supported(d, x, dy)) return 1;
   return x->dtype == COMA_BF16 ? 2 : 3;
 }
@@ -146,7 +157,9 @@ extern "C" int coma_conv_fwd_norm_stats(const coma_conv_desc* d, const coma_tens
   if ((algo_ == 2 && wk_dtype == COMA_BF16) || (algo_ >= 3 && wk_dtype == COMA_F32)) {
     int fused = 0;
     const int inst = mode == COMA_NORM_INSTANCE ? y->B : 0;      // (the kernels' group count; 0 = one BatchNorm group)
-    if (algo_ == 4) {
+    if (pw_fwd(d, x, y)) {
+      if (int rc = conv_pw_f32(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, 0)) return rc;
+    } else if (algo_ == 4) {
       if (int rc = split_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, 0)) return rc;
     } else if (int rc = conv_mfma_fwd(d, x, wk, bias, y, s, (double2*)sums, inst, &fused, ws, ws_bytes, (zeroed & COMA_ZEROED_WS) ? 1 : 0, 0, wk_frag)) return rc;
     if (fused) return 0;
@@ -184,9 +197,10 @@ extern "C" int coma_conv_wgrad(const coma_conv_desc* d, const coma_tensor* x, co
   const int algo = coma_conv_wgrad_algo(d, x, dy);
   if (algo == 4) {
     if (conv_split_wgrad_ok(d, x, dy)) return conv_split_wgrad(d, x, dy, dwk, s, zeroed);
-    if (d->algo == 6 && conv_split_thin_wgrad_ok(d, x, dy)) return conv_split_thin_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);      // (merges into the replica scratch, as algo 0)
+    if (thin_on(d) && conv_split_thin_wgrad_ok(d, x, dy)) return conv_split_thin_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);      // (merges into the replica scratch, as algo 0)
     return conv_split_wgrad2(d, x, dy, dwk, s, zeroed);
   }
+  if (pw_wgrad(d, x, dy)) return conv_pw_f32_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);      // (merges into the replica scratch, as algo 0)
   if (algo >= 2) return conv_mfma_wgrad(d, x, dy, dwk, ws, ws_bytes, s, zeroed);
   return conv_direct_wgrad(d, x, dy, dwk, s, zeroed);
 }

@@ -61,6 +61,14 @@ bool conv_f32_wgrad16s2_problem(const coma_conv_desc* d, const coma_tensor* x, c
 bool conv_f32_thin_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
 bool conv_f32_thin_wgrad_problem(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
 
+// ---- conv_pw_f32.hip (algo 7, pointwise: the 1x1x1 fp32 layers with several channels on both sides, exact fp32 MFMA) ----
+bool conv_pw_f32_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+int conv_pw_f32(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum);
+bool conv_pw_f32_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+int conv_pw_f32_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws, size_t ws_bytes,
+                      hipStream_t s, int zeroed);
+
 // ---- between conv_mfma.hip and conv_wgrad.hip only ----
 // Small weight tensors (the 1..16-channel layers, 1x1x1 gates): a thousand blocks merging into a few cache lines
 // serialise in the L2 atomic unit (1 -> 32 channels at 128^3: 520 us, of which ~400 us were atomics).  Their blocks

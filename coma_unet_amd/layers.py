@@ -32,11 +32,15 @@ class Config:
             raise ValueError("conv_algo=5 (wide split-bf16 convolutions) keeps fp32 tensors: it needs compute_dtype=torch.float32")
         if conv_algo == 6 and compute_dtype != torch.float32:
             raise ValueError("conv_algo=6 (thin split-bf16 convolutions) keeps fp32 tensors: it needs compute_dtype=torch.float32")
+        if conv_algo == 7 and compute_dtype != torch.float32:
+            raise ValueError("conv_algo=7 (pointwise fp32 MFMA convolutions) keeps fp32 tensors: it needs compute_dtype=torch.float32")
         self.compute_dtype = compute_dtype
         # 0 auto, 1 direct VALU fp32, 2 = 0, 4 split: fp32 tensors, the thick stride-1 3^3 layers on the bf16 matrix pipe
         # as a two-term split (the library answers 4 for those layers; their kernel-layout weights stay fp32)
         # 5 wide split: 4 plus the stride-2 data gradients / weight gradients and the transposed up-convolutions
         # 6 thin split: 5 plus the few-channel (C <= 16) full-resolution layers
+        # 7 pointwise: 6 plus the 1x1x1 layers with several channels on both sides (the attention gates' W_g / W_x) on
+        # exact fp32 MFMA kernels of their own (the library answers 3 for those: fp32 kernel-layout weights, as today)
         self.conv_algo = conv_algo
         self.bn_updates_per_forward = bn_updates_per_forward
         self.nbt_pending = None               # list while a model forward collects BatchNorm step counters

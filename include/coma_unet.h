@@ -120,7 +120,17 @@ typedef struct coma_conv_desc {
                              coma_conv_wgrad_algo answer 4 there too (fp32 kernel-layout weights); coma_conv_accumulate_ok,
                              coma_conv_fwd_ws_bytes and coma_conv_wgrad_ws_bytes answer what they answer under algo 0 (the
                              weight gradient merges into the same replica scratch and honours COMA_ZEROED_WS).  Every other
-                             problem, and bf16 tensors, resolve exactly as algo 0 does. */
+                             problem, and bf16 tensors, resolve exactly as algo 0 does.
+                             7 pointwise: everything algo 6 resolves as algo 6 does, plus the 1x1x1 stride-1 layers with
+                             several channels on both sides on fp32 tensors, at >= 4096 voxels per sample, on kernels of
+                             their own on v_mfma_f32_32x32x2_f32 (exact fp32, no split): forward / data gradient for
+                             8 <= C <= 64, C % 8 == 0, 4 <= N <= 64 (not C = 48 or 64 with N = 32), per-sample or shared weights,
+                             COMA_ACCUMULATE and the fused statistics implemented; weight gradient for both channel counts
+                             in 4..64 and multiples of 4.  coma_conv_pick_algo / coma_conv_wgrad_algo answer 3 there (fp32
+                             kernel-layout weights); for such a forward problem coma_conv_accumulate_ok answers 1 and
+                             coma_conv_fwd_ws_bytes 0; the weight gradient merges into the replica scratch
+                             coma_conv_wgrad_ws_bytes / _zs_bytes name and honours COMA_ZEROED_WS / COMA_ZEROED_OUT.  Every
+                             other problem, and bf16 tensors, resolve exactly as algo 6 does. */
 } coma_conv_desc;
 
 int         coma_abi_version(void);
