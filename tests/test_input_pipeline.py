@@ -80,7 +80,9 @@ def test_nifti_reader_and_covariates(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,spacing", [((37, 41, 53), (1.0, 1.0, 1.0)), ((20, 24, 28), (2.0, 2.0, 2.0)),
                                            ((30, 33, 35), (1.2, 0.9375, 1.5)), ((9, 10, 11), (3.0, 3.4, 2.9)),
-                                           ((170, 256, 256), (1.0, 1.0, 1.5))])
+                                           ((170, 256, 256), (1.0, 1.0, 1.5)),
+                                           # 130 x 128 x 128 outputs: more than one pass of the 8192-block grid
+                                           ((65, 64, 64), (4.0, 4.0, 4.0))])
 def test_resample_kernel_bit_exact_vs_oracle(shape, spacing):
     from coma_unet_amd import input_pipeline as P
     from oracle import input_oracle as O
