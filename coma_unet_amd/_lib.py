@@ -113,6 +113,9 @@ SIGNATURES = {
     "coma_event_record_external": (_i32, [_vp, _vp]),
     "coma_stream_wait_external": (_i32, [_vp, _vp]),
     "coma_adamw": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "coma_grad_accum": (_i32, [_vp, _vp, _i64, _vp, _vp, C.POINTER(_i32), _vp]),
+    "coma_adamw_ex": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp, _f32,
+                             _vp, _vp]),
 }
 
 

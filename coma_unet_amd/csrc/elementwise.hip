@@ -493,3 +493,160 @@ extern "C" int coma_adamw(float* p, const float* g, float* m, float* v, int64_t 
   COMA_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- gradient accumulation and global-norm clipping beside adamw_k (optim.FusedAdamW(grad_acc_batch, max_grad_norm)) ----
+// Both kernels are deterministic: every double sum below runs in one fixed order (per thread over its own elements, the
+// xor tree of a wave, the four waves of a block in index order), no atomics.
+enum { ACC_BLOCKS = 1024 };      // grid cap of grad_accum_k == the longest table of partials
+
+__device__ __forceinline__ double ew_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// whole block calls this; every thread gets the sum
+__device__ __forceinline__ double ew_block_sum(double v, double* sh) {
+  v = ew_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// MODE 0: acc = g; 1: acc += g; 2: read g only.  -> this thread's sum of squares (fp64) of the values it handled.
+template <int MODE, bool NORM>
+__device__ __forceinline__ double accum_sweep(float* __restrict__ acc, const float* __restrict__ g, int64_t n, int vec4) {
+  double sq = 0.0;
+  auto one = [&](float a, float gi) {
+    const float r = MODE == 1 ? a + gi : gi;
+    if (NORM) sq += (double)r * (double)r;
+    return r;
+  };
+  auto four = [&](float4 a, const float4 gv) {
+    a.x = one(a.x, gv.x); a.y = one(a.y, gv.y); a.z = one(a.z, gv.z); a.w = one(a.w, gv.w);
+    return a;
+  };
+  const int64_t n4 = vec4 ? n >> 2 : 0;          // 16 bytes per lane and stream where both buffers are 16-byte aligned
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  // two trips of the grid-stride loop at a time: their loads are in flight together (four at a time measured slower for the
+  // plain add)
+  for (; i + stride < n4; i += 2 * stride) {
+    const float4 g0 = g4[i], g1 = g4[i + stride];
+    const float4 a0 = MODE == 1 ? a4[i] : z4, a1 = MODE == 1 ? a4[i + stride] : z4;
+    const float4 r0 = four(a0, g0), r1 = four(a1, g1);
+    if (MODE != 2) { a4[i] = r0; a4[i + stride] = r1; }
+  }
+  if (i < n4) {
+    const float4 r0 = four(MODE == 1 ? a4[i] : z4, g4[i]);
+    if (MODE != 2) a4[i] = r0;
+  }
+  for (i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float r = one(MODE == 1 ? acc[i] : 0.f, g[i]);
+    if (MODE != 2) acc[i] = r;
+  }
+  return sq;
+}
+
+template <bool ACC, bool NORM>
+__global__ __launch_bounds__(256) void grad_accum_k(float* __restrict__ acc, const float* __restrict__ g, int64_t n,
+                                                    const int32_t* __restrict__ count_dev, double* __restrict__ partials, int vec4) {
+  __shared__ double sh[4];
+  double sq;
+  if (!ACC) sq = accum_sweep<2, NORM>(nullptr, g, n, vec4);
+  else if (*count_dev == 0) sq = accum_sweep<0, NORM>(acc, g, n, vec4);     // the window's first micro-batch: nothing of acc is read
+  else sq = accum_sweep<1, NORM>(acc, g, n, vec4);
+  if (NORM) {
+    sq = ew_block_sum(sq, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sq;
+  }
+}
+
+static unsigned accum_grid(int64_t n, int vec4) {
+  int64_t nb = ((vec4 ? (n + 3) / 4 : n) + 255) / 256;
+  if (nb > ACC_BLOCKS) nb = ACC_BLOCKS;
+  return (unsigned)(nb < 1 ? 1 : nb);
+}
+
+extern "C" int coma_grad_accum(float* acc, const float* g, int64_t n, const int32_t* count_dev, double* partials,
+                               int32_t* blocks_out, void* stream) {
+  if (blocks_out) *blocks_out = 0;
+  COMA_CHECK(n >= 0, "grad_accum: n = %lld", (long long)n);
+  if (n == 0) return 0;
+  COMA_CHECK(g && (!acc || count_dev) && (acc || partials), "grad_accum: bad argument");
+  const int vec4 = ((((uintptr_t)acc) | ((uintptr_t)g)) & 15) == 0;
+  const unsigned nb = accum_grid(n, vec4);
+#define L(A, N) hipLaunchKernelGGL((grad_accum_k<A, N>), dim3(nb), dim3(256), 0, (hipStream_t)stream, acc, g, n, count_dev, partials, vec4)
+  if (acc) { if (partials) L(true, true); else L(true, false); }
+  else L(false, true);
+#undef L
+  COMA_LAUNCH_CHECK();
+  if (blocks_out) *blocks_out = (int32_t)nb;
+  return 0;
+}
+
+// adamw_k on g * s, s = clip coefficient / micro-batches in the window (see coma_adamw_ex in coma_unet.h).  Every block
+// forms s from the same table in the same order, so all blocks hold the bitwise-same value.
+__global__ __launch_bounds__(256) void adamw_ex_k(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
+                                                  float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                  const int32_t* step_dev, const int32_t* count_dev, const double* partials,
+                                                  int n_partials, const double* extra_sumsq, float max_norm, float* norm_out,
+                                                  int vec4) {
+  __shared__ double sh[4];
+  if (step_dev) {
+    const float st = (float)*step_dev;
+    bc1 = 1.f - powf(b1, st);
+    bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  }
+  const double count = count_dev ? (double)*count_dev : 1.0;
+  double c = 1.0;
+  if (partials) {                                   // (kernel argument: the whole block takes the branch)
+    double t = 0.0;
+    for (int k = threadIdx.x; k < n_partials; k += 256) t += partials[k];
+    t = ew_block_sum(t, sh);
+    if (extra_sumsq) t += *extra_sumsq;
+    const double norm = sqrt(t) / count;            // of the MEAN gradient: what clip_grad_norm_ returns
+    const double x = (double)max_norm / (norm + 1e-6);
+    c = x > 1.0 ? 1.0 : x;                          // (a NaN stays one: error_if_nonfinite=False)
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
+  }
+  const float s = (float)(c / count);
+  auto upd = [&](float& pi, float gr, float& mi, float& vi) {
+    const float gi = gr * s;
+    pi *= (1.f - lr * wd);
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+  };
+  const int64_t n4 = vec4 ? n >> 2 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    upd(pv.x, gv.x, mv.x, vv.x); upd(pv.y, gv.y, mv.y, vv.y); upd(pv.z, gv.z, mv.z, vv.z); upd(pv.w, gv.w, mv.w, vv.w);
+    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float pi = p[i], mi = m[i], vi = v[i];
+    upd(pi, g[i], mi, vi);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+  }
+}
+extern "C" int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int32_t step, const int32_t* step_dev, const int32_t* count_dev,
+                             const double* partials, int32_t n_partials, const double* extra_sumsq, float max_norm,
+                             float* norm_out, void* stream) {
+  COMA_CHECK(p && g && m && v && n >= 0 && (step >= 1 || step_dev), "adamw_ex: bad argument");
+  COMA_CHECK(!partials || (n_partials >= 0 && n_partials <= ACC_BLOCKS && max_norm >= 0.f),
+             "adamw_ex: %d partials (at most %d), max_norm %g", n_partials, (int)ACC_BLOCKS, (double)max_norm);
+  if (n == 0) return 0;
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2 = 1.f - powf(beta2, (float)step);
+  const int vec4 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
+  hipLaunchKernelGGL(adamw_ex_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
+                     beta2, eps, weight_decay, bc1, sqrtf(bc2), step_dev, count_dev, partials, (int)n_partials, extra_sumsq,
+                     max_norm, norm_out, vec4);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}

@@ -1399,3 +1399,31 @@ def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, step, step_dev=None):
     assert p.is_contiguous() and g.is_contiguous() and p.dtype == torch.float32
     check(lib.coma_adamw(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step, ptr(step_dev),
                          L.stream()), "coma_adamw")
+
+
+ACC_PARTIALS = 1024      # coma_grad_accum's grid cap: the length of a table of partials
+
+
+def grad_accum_(acc, g, count_dev=None, partials=None):
+    """One micro-batch's flat gradient `g` into the window's accumulator: acc = g where the device int32 `count_dev` is 0,
+    else acc += g.  acc=None: the norm-only form (g is only read).  partials: device fp64 [ACC_PARTIALS] or None -- every
+    block stores its sum of squares of the values it handled.  -> the number of live partials (blocks launched)."""
+    assert g.is_contiguous() and g.dtype == torch.float32
+    assert acc is None or (acc.is_contiguous() and acc.dtype == torch.float32 and acc.numel() == g.numel() and count_dev is not None)
+    assert partials is None or (partials.dtype == torch.float64 and partials.numel() >= ACC_PARTIALS)
+    import ctypes
+    nb = ctypes.c_int32(0)
+    check(lib.coma_grad_accum(ptr(acc), ptr(g), g.numel(), ptr(count_dev), ptr(partials), ctypes.byref(nb), L.stream()),
+          "coma_grad_accum")
+    return int(nb.value)
+
+
+def adamw_ex_(p, g, m, v, lr, beta1, beta2, eps, wd, step, step_dev=None, count_dev=None, partials=None, n_partials=0,
+              extra_sumsq=None, max_norm=0.0, norm_out=None):
+    """adamw_ on g * s with s = min(1, max_norm / (norm + 1e-6)) / count: count = the device int32 `count_dev` (None: 1),
+    norm = sqrt(sum of the first n_partials `partials` + the device fp64 `extra_sumsq`) / count, written to the device fp32
+    `norm_out`.  partials=None: no clipping."""
+    assert p.is_contiguous() and g.is_contiguous() and p.dtype == torch.float32 and g.dtype == torch.float32
+    check(lib.coma_adamw_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step, ptr(step_dev),
+                            ptr(count_dev), ptr(partials), n_partials, ptr(extra_sumsq), max_norm, ptr(norm_out), L.stream()),
+          "coma_adamw_ex")

@@ -7,6 +7,11 @@ single HBM-bound kernel launch and the data-parallel gradient exchange can all-r
 contiguous buckets of the same buffer.  Parameters whose gradient is ``None`` are skipped
 exactly as torch does (no decay, no moment update, no step count): the reference model has
 ~75 such tensors ("aux model heads never used in forward").
+
+``grad_acc_batch=K`` / ``max_grad_norm``: gradient accumulation over K micro-batches and global-norm clipping inside the
+step's own kernels (``ops.grad_accum_`` / ``ops.adamw_ex_``), replay-safe.  The gradient applied is the MEAN over the
+window's micro-batches (the ``(loss / K).backward()`` idiom; the reference's commented-out ``grad_acc_batch`` lines,
+attn_unet_data_parallel.py:887-890, do not divide -- the mean keeps ``lr`` comparable across K).
 """
 from __future__ import annotations
 
@@ -15,10 +20,34 @@ import torch
 from . import ops
 
 
+NO_EXCHANGE = ("grad_acc_batch > 1 / max_grad_norm are not supported under a data-parallel gradient exchange (sharded steps, "
+               "GradReducer, StreamedGradExchange): the exchange of an accumulated gradient and the clip of a sharded one are "
+               "not implemented")
+
+
+def _check_window_opts(grad_acc_batch, max_grad_norm):
+    if isinstance(grad_acc_batch, bool) or int(grad_acc_batch) != grad_acc_batch or int(grad_acc_batch) < 1:
+        raise ValueError(f"grad_acc_batch must be an integer >= 1, got {grad_acc_batch!r}")
+    if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+        raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm!r}")
+
+
+def check_no_exchange(optimizer, reducer):
+    """ValueError when a gradient exchange meets an optimizer that accumulates or clips."""
+    if reducer is not None and getattr(optimizer, "windowed", False):
+        raise ValueError(NO_EXCHANGE)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, dynamic=(), write_through=False,
-                 pad_to=1):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+                 pad_to=1, grad_acc_batch=1, max_grad_norm=None):
+        """grad_acc_batch=K > 1: ``step()`` means "this micro-batch's backward is done" -- it adds the flat gradient to a flat
+        fp32 accumulator and the K-th call (or ``flush()``) applies ONE update with the MEAN of the window's gradients.
+        max_grad_norm: clip that mean gradient to this global 2-norm first (``torch.nn.utils.clip_grad_norm_``; the
+        unclipped norm is left in ``last_grad_norm``, a device float).  Both live in ``param_groups[0]``."""
+        _check_window_opts(grad_acc_batch, max_grad_norm)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_acc_batch=int(grad_acc_batch),
+                        max_grad_norm=None if max_grad_norm is None else float(max_grad_norm))
         super().__init__(params, defaults)
         assert len(self.param_groups) == 1, "one parameter group (the reference uses one)"
         self._dynamic = {id(p) for p in dynamic}   # may or may not get a gradient, step to step
@@ -40,6 +69,16 @@ class FusedAdamW(torch.optim.Optimizer):
         self._zero_tab = None          # (device int64 [n, 2] table, n, longest range)
         self._zero_big = ()            # ids of the parameters zero_grad() skips
         self.sparse_zero = True
+        # accumulation window / clipping (allocated on first use; none of it exists on the default path)
+        self.flat_acc = None           # fp32 accumulator with flat_g's layout (grad_acc_batch > 1)
+        self._acc_dev = None           # device int32: micro-batches in the open window (a captured step keeps counting under replay)
+        self._pending = 0              # its host copy
+        self._partials = None          # device fp64 [ops.ACC_PARTIALS]: per-block sums of squares of the gradient to clip
+        self._extra_dev = None         # device fp64: squared norm of the gradients outside the flat buffer
+        self._norm_dev = None          # device fp32: what coma_adamw_ex wrote (the unclipped norm of the mean gradient)
+        self._loose_acc = {}           # parameter outside the flat buffer -> its fp32 accumulator (all zeros between windows)
+        self._loose_live = set()       # ids of those that received a gradient in the open window
+        self.last_grad_norm = None
 
     # -- layout -------------------------------------------------------------------------
     def _build(self):
@@ -113,6 +152,11 @@ class FusedAdamW(torch.optim.Optimizer):
         (they live, up to date, on the ranks that own them).  A step may also be taken slice by slice as the slices'
         gradients arrive (GradReducer.reduce_flat_and_step): advance=True on the first call only (the step count moves
         once), loose=True on one call only (parameters outside the flat buffer)."""
+        if self.windowed:         # grad_acc_batch > 1 or max_grad_norm: the step goes through the window
+            if shards is not None or not (advance and loose) or self.shard_exchange is not None:
+                raise ValueError(NO_EXCHANGE)
+            ops.SidePrep.join()
+            return self._micro_step()
         ops.SidePrep.join()       # the side stream's expert-gradient scatters land in the flat gradient buffer
         g = self.param_groups[0]
         lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
@@ -144,6 +188,115 @@ class FusedAdamW(torch.optim.Optimizer):
             gr = p.grad.float().contiguous()
             ops.adamw_(p.data.view(-1), gr.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps,
                        wd, st["step"])
+
+    # -- accumulation window and clipping ----------------------------------------------
+    def _window_opts(self):
+        g = self.param_groups[0]
+        K, mx = g.get("grad_acc_batch", 1), g.get("max_grad_norm")
+        _check_window_opts(K, mx)
+        return int(K), (None if mx is None else float(mx))
+
+    @property
+    def windowed(self):
+        """Either new option is on: step() goes through coma_grad_accum / coma_adamw_ex instead of coma_adamw."""
+        K, mx = self._window_opts()
+        return K > 1 or mx is not None
+
+    @property
+    def pending(self):
+        """Micro-batches in the open window (0: the last step() or flush() applied an update)."""
+        return self._pending
+
+    def _ensure_window_buffers(self):
+        """The window's device state, allocated outside any graph capture (a counter created under capture would be
+        re-created, not advanced, by every replay)."""
+        K, mx = self._window_opts()
+        dev = self.flat_g.device
+        if K > 1 and self.flat_acc is None:
+            self.flat_acc = torch.zeros_like(self.flat_g)
+        if self._acc_dev is None:
+            self._acc_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        if mx is not None and self._partials is None:
+            self._partials = torch.zeros(ops.ACC_PARTIALS, dtype=torch.float64, device=dev)
+            self._extra_dev = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._norm_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def _micro_step(self):
+        """This micro-batch's backward is done: into the window; the grad_acc_batch-th one applies the update."""
+        K, mx = self._window_opts()
+        if not self.built:
+            self._build()
+        self._ensure_window_buffers()
+        self._sparse_zero_bookkeeping()
+        apply = self._pending + 1 >= K
+        nb = None
+        if K > 1:
+            # flat_g keeps this micro-batch's own gradient; the partials of the K-th launch are those of the finished sum
+            nb = ops.grad_accum_(self.flat_acc, self.flat_g, self._acc_dev, self._partials if (apply and mx is not None) else None)
+            self._acc_dev += 1
+            for p in self.param_groups[0]["params"]:
+                if id(p) in self._flat_ids or p.grad is None:
+                    continue
+                acc = self._loose_acc.get(p)
+                if acc is None:
+                    acc = self._loose_acc[p] = torch.zeros_like(p, dtype=torch.float32).view(-1)
+                acc.add_(p.grad.float().reshape(-1))        # (0 + g is exact: the window's first gradient is assigned)
+                self._loose_live.add(id(p))
+        self._pending += 1
+        if apply:
+            self._apply(K, mx, nb)
+        else:
+            ops.ZeroArena.end_step()
+
+    def flush(self):
+        """Apply an open window of fewer than grad_acc_batch micro-batches (the mean over those it holds).  No-op when
+        nothing is pending."""
+        if self._pending == 0:
+            return
+        K, mx = self._window_opts()
+        with torch.no_grad():
+            self._apply(K, mx, None)
+
+    def _apply(self, K, mx, nb):
+        g = self.param_groups[0]
+        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
+        acc_mode = K > 1
+        src = self.flat_acc if acc_mode else self.flat_g
+        count_dev = self._acc_dev if acc_mode else None
+        if acc_mode:
+            loose_src = [(p, self._loose_acc[p]) for p in g["params"] if id(p) in self._loose_live]
+        else:
+            loose_src = [(p, p.grad.float().contiguous().view(-1)) for p in g["params"]
+                         if id(p) not in self._flat_ids and p.grad is not None]
+        partials, n_part, extra, norm_out = None, 0, None, None
+        if mx is not None:
+            if nb is None:                 # flush(), or no accumulation: a norm-only pass over the gradient source
+                nb = ops.grad_accum_(None, src, None, self._partials)
+            partials, n_part, norm_out = self._partials, nb, self._norm_dev
+            if loose_src:
+                self._extra_dev.copy_(torch.stack([a.double().pow(2).sum() for _, a in loose_src]).sum().view(1))
+                extra = self._extra_dev
+        self._flat_step += 1
+        self._step_dev += 1                # once per applied update (torch's step count under the usual accumulation idiom)
+        ops.adamw_ex_(self.flat_p, src, self.flat_m, self.flat_v, lr, b1, b2, eps, wd, self._flat_step, self._step_dev,
+                      count_dev, partials, n_part, extra, mx or 0.0, norm_out)
+        ops.ZeroArena.end_step()           # (behind the sweep, as in step_shards)
+        for p, a in loose_src:
+            st = self.state[p]
+            if not st:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
+                st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
+            st["step"] += 1
+            ops.adamw_ex_(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps, wd,
+                          st["step"], None, count_dev, partials, n_part, extra, mx or 0.0, None)
+        if acc_mode:
+            self._acc_dev.zero_()
+            for _, a in loose_src:
+                a.zero_()
+            self._loose_live.clear()
+        self._pending = 0
+        self.last_grad_norm = norm_out
 
     def _sparse_zero_bookkeeping(self):
         """After a backward: (1) any large tensor zero_grad() skipped that the kernels did NOT overwrite this step still
@@ -183,6 +336,9 @@ class FusedAdamW(torch.optim.Optimizer):
         """torch.optim.AdamW's format.  Under a sharded exchange the moments of this rank's sub-slices are current and the
         others stopped at the last unsharded step: they are all-gathered first (every rank must call state_dict(), like any
         collective; afterwards every rank holds the full, identical state)."""
+        if self._pending:
+            raise RuntimeError(f"FusedAdamW.state_dict(): {self._pending} micro-batch(es) of an open accumulation window are "
+                               "not applied yet -- call flush() first")
         if self.shard_exchange is not None and self.built:
             self.shard_exchange.gather_state()
         params = self.param_groups[0]["params"]

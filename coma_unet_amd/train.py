@@ -10,16 +10,19 @@ import os
 import torch
 
 from . import ops
-from .optim import FusedAdamW
+from .optim import FusedAdamW, check_no_exchange
 from .data_parallel import GradReducer, StreamedGradExchange
 
 
-def make_optimizer(model, lr=1e-3, write_through=True, pad_to=1):
+def make_optimizer(model, lr=1e-3, write_through=True, pad_to=1, grad_acc_batch=1, max_grad_norm=None):
     """torch.optim.AdamW(model.parameters(), lr) of :736, fused.  ``write_through``: parameter gradients are
     written by the backward kernels straight into the optimizer's flat gradient buffer (see ops.GradSink).
-    ``pad_to``: the world size when the step is sharded over ranks (StreamedGradExchange(sharded=True))."""
+    ``pad_to``: the world size when the step is sharded over ranks (StreamedGradExchange(sharded=True)).
+    ``grad_acc_batch`` / ``max_grad_norm``: one update per grad_acc_batch steps with the mean of their gradients, clipped
+    to that global norm (optim.FusedAdamW; the reference's commented-out accumulation, :887-890, :918-920)."""
     dyn = [model.pos_dynamic_prompt, model.neg_dynamic_prompt] if not getattr(model, "static_prompts", False) else []
-    return FusedAdamW(model.parameters(), lr=lr, dynamic=dyn, write_through=write_through, pad_to=pad_to)
+    return FusedAdamW(model.parameters(), lr=lr, dynamic=dyn, write_through=write_through, pad_to=pad_to,
+                      grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm)
 
 
 def forward_loss(model, criterion, batch, global_rnc=False):
@@ -41,6 +44,7 @@ def forward_loss(model, criterion, batch, global_rnc=False):
 
 
 def train_step(model, criterion, optimizer, batch, reducer: GradReducer = None, global_rnc=False):
+    check_no_exchange(optimizer, reducer)
     if reducer is not None and reducer.world > 1:
         # every rank must reduce the same tensors in the same order: with rank-local prompt selection the two
         # selectable prompts get grad=None on some ranks only (attn_unet_data_parallel.py:638-639) and the collective
@@ -78,6 +82,7 @@ class GraphedTrainStep:
         exists, the workspaces are sized): capture without any warm-up step, so that no optimizer step is taken here
         (train_loop.train_dp, where every step must be a real one on real data)."""
         assert getattr(model, "static_prompts", False), "graph capture needs static_prompts=True"
+        check_no_exchange(optimizer, reducer)
         self.model, self.criterion, self.optimizer, self.reducer = model, criterion, optimizer, reducer
         self.batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in batch.items()}
         assert torch.is_tensor(self.batch["roi_pred_dicts"]), "pass ROI priors as a (B, 36, 2) device tensor"
@@ -103,7 +108,8 @@ class GraphedTrainStep:
 
     def _hyper(self):
         g = self.optimizer.param_groups[0]
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]))
+        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), g.get("grad_acc_batch", 1),
+                g.get("max_grad_norm"))
 
     def _capture(self):
         """(Re)capture.  The optimizer's hyper-parameters are kernel arguments frozen into the graph, so a change of
@@ -115,6 +121,12 @@ class GraphedTrainStep:
         if reducer is not None and not self.in_graph and hasattr(reducer, "graph_watch"):
             self.watch = reducer.graph_watch(self.batch["mri"].device)
         self.graph = torch.cuda.CUDAGraph()
+        self.micro_graph = None
+        K = int(optimizer.param_groups[0].get("grad_acc_batch", 1))
+        if K > 1:
+            return self._capture_window(K)
+        if optimizer.windowed:
+            optimizer._ensure_window_buffers()
         # thread_local: the RCCL watchdog thread may query events while this thread captures
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             if reducer is None or self.in_graph:
@@ -135,6 +147,27 @@ class GraphedTrainStep:
             # capture executes nothing: undo the host-side step count train_step's optimizer.step() just added
             optimizer._flat_step -= 1
 
+    def _capture_window(self, K):
+        """grad_acc_batch > 1: two graphs out of one memory pool -- `micro_graph` (zero_grad + forward + loss + backward +
+        accumulate + counter) and `graph`, the applying one (the same, then norm + update + counter reset).  The
+        accumulate kernel reads the window's position from the device counter, so the micro graph serves every
+        micro-batch but the last.  Capture executes nothing: the host counters go back to where they were."""
+        optimizer = self.optimizer
+        optimizer._ensure_window_buffers()
+        host = (optimizer._flat_step, optimizer._pending)
+        try:
+            optimizer._pending = 0
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self.micro_result = train_step(self.model, self.criterion, optimizer, self.batch)
+            assert optimizer._pending == 1
+            self.micro_graph, self.graph = self.graph, torch.cuda.CUDAGraph()
+            optimizer._pending = K - 1
+            with torch.cuda.graph(self.graph, pool=self.micro_graph.pool(), capture_error_mode="thread_local"):
+                self.losses, self.outputs = train_step(self.model, self.criterion, optimizer, self.batch)
+            assert optimizer._pending == 0
+        finally:
+            optimizer._flat_step, optimizer._pending = host
+
     def load(self, batch):
         for k, v in batch.items():
             if torch.is_tensor(v):
@@ -146,6 +179,16 @@ class GraphedTrainStep:
         whole = self.reducer is None or self.in_graph
         if whole and self._hyper() != self._captured_hyper:
             self._capture()
+        if self.micro_graph is not None:
+            opt = self.optimizer
+            if opt.pending + 1 < self._captured_hyper[4]:          # not the window's last micro-batch
+                self.micro_graph.replay()
+                opt._pending += 1
+                return self.micro_result
+            self.graph.replay()
+            opt._pending = 0
+            opt._flat_step += 1
+            return self.losses, self.outputs
         self.graph.replay()
         if whole:
             self.optimizer._flat_step += 1

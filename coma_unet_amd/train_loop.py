@@ -27,6 +27,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import metrics as M
 from .checkpoint import save_checkpoint
+from .optim import NO_EXCHANGE, check_no_exchange
 from .train import make_optimizer, train_step, GraphedTrainStep
 
 
@@ -98,7 +99,12 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        reducer's (its flat layout is what the reducer buckets); the plateau scheduler sees the loss of the GLOBAL
        batch (all-reduced sums), so every rank keeps the same learning rate; checkpoints, CSVs and validation are rank 0's
        (``optimizer.state_dict()`` is still called by every rank: it is a collective under a sharded exchange).
-     * ``optimizer``: use this FusedAdamW instead of building one (``from_checkpoint=True`` requires it, as upstream)."""
+     * ``optimizer``: use this FusedAdamW instead of building one (``from_checkpoint=True`` requires it, as upstream).
+     * ``grad_acc_batch`` / ``max_grad_norm``: passed to ``make_optimizer`` when the optimizer is built here (a caller's own
+       optimizer keeps its own settings): one update per ``grad_acc_batch`` batches with the mean of their gradients,
+       clipped to that global norm.  A window still open at the end of an epoch is applied there (``optimizer.flush()``,
+       the reference's "ensure BP on the remaining accumulated batches", :918-920), before the scheduler step and the
+       checkpoint.  Not available together with ``reducer`` (ValueError)."""
     import torch.distributed as dist
     cwd = os.getcwd()
     fold = kwargs.get("fold_id")
@@ -114,6 +120,9 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     checkpoint_iter = val_iter
     start_epoch = 0
     reducer = kwargs.get("reducer")
+    grad_acc_batch, max_grad_norm = kwargs.get("grad_acc_batch", 1), kwargs.get("max_grad_norm")
+    if reducer is not None and (grad_acc_batch != 1 or max_grad_norm is not None):
+        raise ValueError(NO_EXCHANGE)
     world, rank = _dist_info(reducer)
     if from_checkpoint:                                                                                   # :729-733
         optimizer = kwargs["optimizer"]
@@ -126,10 +135,11 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
         elif reducer is not None:
             optimizer = reducer.opt           # the reducer buckets THIS optimizer's flat gradient buffer
         else:
-            optimizer = make_optimizer(model, lr)
+            optimizer = make_optimizer(model, lr, grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm)
         for g in optimizer.param_groups:
             g["lr"] = lr
         scheduler = ReduceLROnPlateau(optimizer, "min", patience=5)
+    check_no_exchange(optimizer, reducer)
     if reducer is not None:
         assert reducer.opt is optimizer, "train_dp(reducer=...) must step the optimizer the reducer was built on"
     use_graph = kwargs.get("graph", "auto")
@@ -201,6 +211,8 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
                 elif a == 0:
                     epoch_neg += gl[b] + ds
                     n_neg += 1
+        if hasattr(optimizer, "flush"):
+            optimizer.flush()             # :918-920: the epoch's last, shorter window is applied, not carried over or dropped
         if world > 1:
             # the plateau scheduler must see the same number on every rank, or the replicas' learning rates drift apart:
             # the loss of the GLOBAL batch (what the reference's single process would have accumulated)

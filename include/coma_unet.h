@@ -370,6 +370,33 @@ int coma_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr
                float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
                void* stream);
 
+/* ---- gradient accumulation and global-norm clipping on the same flat buffers (FusedAdamW(grad_acc_batch,
+ *      max_grad_norm)).  Both calls are deterministic (no atomics; every sum runs in one fixed order).
+ * coma_grad_accum: one micro-batch's gradient g (length n) into the window's accumulator.  count_dev (device int32) =
+ *   micro-batches already in the window, read ON THE DEVICE: 0 -> acc = g (acc is not read), else acc += g (one fp32
+ *   rounding), so that one captured graph serves every micro-batch of a window.  acc == NULL: norm-only form, g is read
+ *   and nothing but `partials` is written.  partials (device fp64, room for 1024; NULL: no norm wanted): block b stores
+ *   (plain store) its fp64 sum of x^2 over the values it handled (the new acc, or g in the norm-only form) to
+ *   partials[b].  The grid is at most 1024 blocks of 256 threads; *blocks_out (host int32, may be NULL) receives the
+ *   number launched = the number of live partials -- the slots behind them are neither written here nor to be read.
+ *   n == 0: no launch, *blocks_out = 0.  16-byte accesses where acc and g are 16-byte aligned, scalar otherwise. ---- */
+int coma_grad_accum(float* acc, const float* g, int64_t n, const int32_t* count_dev, double* partials,
+                    int32_t* blocks_out, void* stream);
+/* coma_adamw_ex: coma_adamw on the gradient g * s, s = c / count rounded once to fp32:
+ *   count = *count_dev (device int32, micro-batches in the window; NULL: 1);
+ *   norm  = sqrt(sum partials[0 .. n_partials) + *extra_sumsq) / count   (fp64; extra_sumsq: device fp64, may be NULL --
+ *           the squared norm of gradients that live outside this buffer);
+ *   c     = min(1, max_norm / (norm + 1e-6)), or 1 when partials == NULL (no clipping)
+ *   -- torch.nn.utils.clip_grad_norm_(.., max_norm, norm_type=2) on the MEAN gradient of the window, a non-finite norm
+ *   included (error_if_nonfinite=False: the coefficient becomes NaN).  Every block sums the partials in the same order, so
+ *   all blocks use the bitwise-same s.  norm_out (device fp32, may be NULL): block 0 stores `norm`, the unclipped norm of
+ *   the mean gradient.  Slots of `partials` at or beyond n_partials (<= 1024) are not read.  With count == 1 and c == 1
+ *   the results are bitwise those of coma_adamw. ---- */
+int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                  const int32_t* count_dev, const double* partials, int32_t n_partials,
+                  const double* extra_sumsq, float max_norm, float* norm_out, void* stream);
+
 /* ---- 3-D SSIM (MONAI SSIMMetric(spatial_dims=3), attn_unet_data_parallel.py:1176,1234) ----
  * x, y: single-channel volumes; window: `win` (<= 11) separable weights (host pointer); c1 = (k1 R)^2, c2 = (k2 R)^2.
  * Writes one fp64 partial sum of the SSIM map per 8^3 output tile: partial[b * ntiles + t]; the per-sample SSIM is
