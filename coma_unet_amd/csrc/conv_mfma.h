@@ -1,4 +1,5 @@
-// What conv_mfma.hip and conv_wgrad.hip share, and the convolution entry points api.hip and conv_split.hip call.
+// What conv_mfma.hip and the files cut out of it (conv_duo.hip, conv_tconv.hip, conv_wgrad.hip) share, and the convolution
+// entry points api.hip and conv_split.hip call.
 #pragma once
 #include "common.h"
 #include "conv_tiles.h"   // bf16x8_t / f32x16_t, stat_add, xcd_remap, tile_coords, tile_run, set_max_lds
@@ -69,7 +70,44 @@ bool conv_pw_f32_wgrad_ok(const coma_conv_desc* d, const coma_tensor* x, const c
 int conv_pw_f32_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws, size_t ws_bytes,
                       hipStream_t s, int zeroed);
 
-// ---- between conv_mfma.hip and conv_wgrad.hip only ----
+// Everything below crosses a file boundary inside the library only (hidden: not part of its symbol table).
+#pragma GCC visibility push(hidden)
+// ---- between conv_mfma.hip (conv_mfma_halo2_k; conv_mfma_halo<T> fills the fields the two kernels share) and conv_duo.hip ----
+struct Halo2P {
+  const void* x; int ldx; long sbx; int D, H, W, C;
+  void* y; int ldy; long sby; int N;
+  const void* w; long wsb;
+  const float* bias; int bsb;
+  int flip, vecx, vecw;
+  int ntx, nty, ntz, ids_total, ids_per_block;
+  unsigned xbytes, wbytes;   // bytes of one sample of x / of one weight set (buffer descriptors: out-of-range pieces read as zero)
+  int st8;             // output rows allow aligned 8-byte (4-channel) stores
+  int st16;            // ... and aligned 16-byte (8-channel) stores
+  double2* stats;      // optional: per-block {sum, sumsq} of the stored outputs, [chunk][G][N]
+  int stats_inst;      // B: groups = the B samples (InstanceNorm), 0: one group (BatchNorm)
+  const void* wfrag;   // conv_mfma_duo_k, C >= 64: the weights re-laid in fragment order (duo_relayout_k), else null
+  long wfrag_sb;       // ... elements between two samples' weight sets
+};
+size_t duo_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+bool duo_wide_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+// q: the common fields of conv_mfma_halo<bf16_t>; thin / vec / lx as there
+bool duo_takes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y, const Halo2P& q, bool thin, bool vec, bool wk_frag,
+               const void* ws, size_t ws_bytes, size_t* frag_bytes_out);
+int launch_duo(const coma_conv_desc* d, const coma_tensor* x, Halo2P q, const void* wk, int lx, int nblk_n, size_t frag_bytes, void* ws,
+               bool wk_frag, hipStream_t s);
+
+// ---- conv_tconv.hip ----
+bool tconv_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y);
+template <typename T>
+int conv_mfma_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
+                    hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum);
+
+// ---- conv_wgrad.hip ----
+bool wgrad_plan_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+int conv_wgrad_planned(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
+                       size_t ws_bytes, hipStream_t s, int zeroed);
+
+// ---- the weight-gradient launchers whose blocks merge with atomics ----
 // Small weight tensors (the 1..16-channel layers, 1x1x1 gates): a thousand blocks merging into a few cache lines
 // serialise in the L2 atomic unit (1 -> 32 channels at 128^3: 520 us, of which ~400 us were atomics).  Their blocks
 // merge into WGRAD_NREP replicas in the workspace instead, summed by one tiny kernel.
@@ -78,10 +116,18 @@ int conv_pw_f32_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_
 static inline long wgrad_out_elems(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {
   return (long)d->ksize * d->ksize * d->ksize * dy->C * x->C * (d->per_sample_w ? x->B : 1);
 }
-// (hidden: not part of the library's symbol table)
-#pragma GCC visibility push(hidden)
-bool wgrad_plan_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
-int conv_wgrad_planned(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
-                       size_t ws_bytes, hipStream_t s, int zeroed);
 int wgrad_replica_sum(const float* rep, long wsz, float* dwk, hipStream_t s);      // (conv_mfma.hip)
+// Where a launcher's blocks merge their wsz outputs: WGRAD_NREP replicas in ws when the output is small, the workspace is
+// there and `allow`, else dwk itself; cleared here unless `zeroed` says the caller did (COMA_ZEROED_WS / COMA_ZEROED_OUT).
+// out == nullptr: the memset failed (error set; return 2).  After the kernel: wgrad_replicas_done().
+struct WgradRep { float* out; int nrep; long rep_stride; };
+static inline WgradRep wgrad_replicas(long wsz, float* dwk, void* ws, size_t ws_bytes, hipStream_t s, int zeroed, bool allow = true) {
+  const bool replicas = allow && wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
+  WgradRep r = {replicas ? (float*)ws : dwk, replicas ? WGRAD_NREP : 1, replicas ? wsz : 0};
+  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(r.out, 0, sizeof(float) * wsz * r.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); r.out = nullptr; }
+  return r;
+}
+static inline int wgrad_replicas_done(const WgradRep& r, long wsz, float* dwk, hipStream_t s) {
+  return r.nrep > 1 ? wgrad_replica_sum(r.out, wsz, dwk, s) : 0;
+}
 #pragma GCC visibility pop

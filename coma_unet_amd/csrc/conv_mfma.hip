@@ -9,31 +9,11 @@
 //
 // Replaces the cuDNN dispatches behind nn.Conv3d / nn.ConvTranspose3d forward and data-gradient
 // in the reference model (attn_unet_data_parallel.py; MONAI Convolution / CondConv call sites).
-// Further down: the stride-1 and voxels-along-K weight-gradient kernels and the dispatch of all of them; the two
-// weight-gradient kernels on 32 x 32 tiles chosen by wgrad_plan (conv_mfma_wgrad_k, conv_f32_wgrad_k) are in conv_wgrad.hip.
-#include "conv_mfma.h"   // load8 / mask8, aligned16, s4_t, the replica constants; conv_tiles.h: tile_run, set_max_lds, stat_add, ...
+// Further down: the stride-1 and voxels-along-K weight-gradient kernels and the dispatch of all of them.  In files of their own:
+// conv_mfma_duo_k (conv_duo.hip), conv_mfma_tconv_k (conv_tconv.hip) and the two weight-gradient kernels on 32 x 32 tiles chosen
+// by wgrad_plan (conv_mfma_wgrad_k, conv_f32_wgrad_k: conv_wgrad.hip).
+#include "conv_mfma.h"   // load8 / mask8, aligned16, s4_t, Halo2P, the replica helper; conv_tiles.h: elem, mma_piece, tile_run, set_max_lds, ...
 #include <type_traits>
-
-// ---- element type of the activations / kernel-layout weights: bf16 (v_mfma_f32_32x32x16_bf16) or fp32
-// (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, 1/16 of the bf16 rate -- the "fp32 mode" of the model,
-// north_star's 1e-3 tolerance path).  Both use the SAME LDS images: a row is 64 bytes = 4 pieces of 16 bytes
-// (32 bf16 or 16 fp32 channels), and the 16-byte fragment a lane reads feeds one bf16 MFMA (K = 16: lane half h holds
-// k = 8h..8h+7) or four fp32 MFMAs (K = 2 each: MFMA m takes channel 4h + m of the piece from lane half h, so the
-// K pair of MFMA m is {m, 4 + m} of the 8 channels the two halves read -- the same for both operands).
-template <typename T> struct elem;
-template <> struct elem<bf16_t> { static constexpr int EPB = 8; };    // elements per 16-byte piece
-template <> struct elem<float> { static constexpr int EPB = 4; };
-
-__device__ __forceinline__ f32x16_t mma_piece(const uint4& a, const uint4& b, f32x16_t acc, bf16_t) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16_t mma_piece(const uint4& a, const uint4& b, f32x16_t acc, float) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  return acc;
-}
 
 struct GatherP {
   const void* x; int ldx; long sbx; int Di, Hi, Wi, C;
@@ -465,22 +445,6 @@ extern "C" int coma_debug_read_stamps(unsigned long long* out16, int reset) {
 #define STAMP(var)
 #define STAMP_ADD(slot, a, b)
 #endif
-
-struct Halo2P {
-  const void* x; int ldx; long sbx; int D, H, W, C;
-  void* y; int ldy; long sby; int N;
-  const void* w; long wsb;
-  const float* bias; int bsb;
-  int flip, vecx, vecw;
-  int ntx, nty, ntz, ids_total, ids_per_block;
-  unsigned xbytes, wbytes;   // bytes of one sample of x / of one weight set (buffer descriptors: out-of-range pieces read as zero)
-  int st8;             // output rows allow aligned 8-byte (4-channel) stores
-  int st16;            // ... and aligned 16-byte (8-channel) stores
-  double2* stats;      // optional: per-block {sum, sumsq} of the stored outputs, [chunk][G][N]
-  int stats_inst;      // B: groups = the B samples (InstanceNorm), 0: one group (BatchNorm)
-  const void* wfrag;   // conv_mfma_duo_k, C >= 64: the weights re-laid in fragment order (duo_relayout_k), else null
-  long wfrag_sb;       // ... elements between two samples' weight sets
-};
 
 // CK = channels per LDS row (bf16: 32, or 16 for the thin full-resolution layers: one MFMA K step per tap; fp32: 16);
 // VEC = every piece is a legal, fully valid 16-byte load; OCC = blocks per CU; T = element type (see `elem`).
@@ -984,382 +948,6 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_halo2_k(Halo2P p) {
       for (int w = 0; w < 4; ++w) { a += (double)red[(w * 32 + tid) * 2]; c += (double)red[(w * 32 + tid) * 2 + 1]; }
       const int g = p.stats_inst ? b : 0;
       stat_add(p.stats, p.stats_inst ? p.stats_inst : 1, p.N, g, n0 + tid, a, c);
-    }
-  }
-}
-
-// =====================================================================================
-// conv_mfma_duo_k -- the thick stride-1 3x3x3 kernel as TWO 4-wave groups per CU that alternate roles every phase.
-// conv_mfma_halo2_k runs one 4-wave block per CU, and its phases do not overlap: stamped, the MFMA loop is 55 % of the
-// kernel, LDS staging stores 18 %, the epilogue 13 %, barriers and waits 14 % -- the matrix pipe idles 45 % of the time.
-// Here a workgroup has 8 waves = 2 groups (each SIMD holds one wave of either group).  In a phase one group runs the 54
-// MFMAs of a (tile, 16-channel chunk) step out of ITS halo image while the other group does everything else for its own
-// next step: writes the halo chunk it fetched two phases ago into its image, writes its half of the next chunk's weights,
-// finishes a completed tile (bias, rounding, statistics, 16-byte stores) and issues the loads of the step after next.  One
-// workgroup barrier per phase; the loads stay in flight across barriers (raw s_barrier behind an LDS-only wait).
-//   LDS: 2 halo images of 816 rows x 48 B (16 channels + pad: 16 consecutive rows land on 16 distinct 16-byte slots)
-//        + 2 weight images of 27 taps x 64 lanes x 16 B in FRAGMENT order (a wave's read is 1 KB contiguous) = 130.5 KB.
-//   The two groups walk alternate tiles of the block's run and the same chunk sequence, so a weight image serves both
-//   (phases 2s and 2s + 1) while the other one is refilled, half by either group.  C == 32: the two images hold the
-//   layer's two chunks for the whole kernel.
-//   A wave's two M-tiles are y-neighbours: for a fixed (kz, kx) their three ky taps read four distinct halo rows, so a
-//   (kz, kx) group is 4 + 3 fragment reads for 6 MFMAs.
-// =====================================================================================
-// wk[b][tap][N][C] -> [b][n tile][16-channel chunk][tap][lane = (n & 31) + 32 * ((c >> 3) & 1)][8 channels]: the order in which
-// conv_mfma_duo_k holds a weight image in LDS, so that a group's half image is ONE contiguous 13.8 KB run (from the plain
-// layout a 16-channel piece is 32 bytes of a 2 C-byte row: at C = 64 the staging group pulled 4x the useful bytes through L1)
-__global__ __launch_bounds__(256) void duo_relayout_k(const uint4* __restrict__ src, uint4* __restrict__ dst, int N, int C8, long total) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;      // piece (b, tap, n, c8)
-  if (i >= total) return;
-  const int c8 = (int)(i % C8);
-  long t = i / C8;
-  const int n = (int)(t % N); t /= N;
-  const int tap = (int)(t % 27);
-  const long b = t / 27;
-  const int nt = N >> 5, nch = C8 >> 1;
-  const long o = ((((b * nt + (n >> 5)) * nch + (c8 >> 1)) * 27 + tap) * 64) + (n & 31) + 32 * (c8 & 1);
-  dst[o] = src[i];
-}
-
-__device__ __forceinline__ void duo_barrier() {
-  // LDS traffic of this wave has landed; buffer loads issued for later phases stay in flight (no vmcnt wait)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// LX = 5: tiles of 2 x 4 x 32 voxels (W >= 32); LX = 4: 2 x 8 x 16 (the 16^3 level: an M-tile is two x-rows of 16 voxels)
-template <int STATS, int LX = 5>
-__global__ __launch_bounds__(512, 1) void conv_mfma_duo_k(Halo2P p) {
-  constexpr int TX = 1 << LX, RY = 32 / TX, TY = 4 * RY, TZ = 2, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HV = HX * HY * HZ;
-  static_assert(HV <= 816, "the halo image is sized for the 2 x 4 x 32 tile");
-  constexpr int P = 48, HB = 816 * P, WB = 27 * 64 * 16;
-  constexpr int HP = HV * 2, HIT = (HP + 255) / 256;        // halo pieces of a 16-channel chunk; per thread of a group
-  constexpr int WH = 27 * 32, WIT = (WH + 255) / 256;       // weight pieces per half image; per thread of a group
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // the wave index through readfirstlane: everything derived from it (group, tile walk, descriptors, role branches) is
-  // then provably wave-uniform -- otherwise the compiler wraps every buffer load in a waterfall loop
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wid >> 2, wq = wid & 3, gt = tid & 255;
-  char* const Hl = smem + grp * HB;
-  char* const Wl = smem + 2 * HB;
-  const int b = blockIdx.z, n0 = blockIdx.y * 32;
-  const int fr = lane & 31, fh = lane >> 5;
-  const bf16_t* xb = static_cast<const bf16_t*>(p.x) + (long)b * p.sbx;
-  const bf16_t* wb = static_cast<const bf16_t*>(p.w) + (long)b * p.wsb;
-  bf16_t* yb = static_cast<bf16_t*>(p.y) + (long)b * p.sby;
-  const int nch = p.C >> 4;
-  const bool w_static = nch <= 2;
-
-  // ---- staging descriptors ----
-  // Halo piece `it` of this thread is row (gt >> 1) + 128 it, half gt & 1.  Its halo coordinates and global offset are
-  // rebuilt from the FIRST piece's coordinates at every fetch (row + 128 = 3 x-lines + 26: a few adds and compares per
-  // piece on the staging wave) instead of living in 14 registers: at two waves per SIMD registers are the scarce thing.
-  const int h_row0 = gt >> 1, h_half = gt & 1;
-  unsigned h_zyx0 = ((unsigned)(h_row0 / (HX * HY)) << 20) | ((unsigned)((h_row0 / HX) % HY) << 10) | (unsigned)(h_row0 % HX);
-  // in-volume test of a halo piece as two packed subtractions (fields of 9 bits under a guard bit each): halo coordinate h
-  // of a tile at origin o is inside iff lo <= h <= hi with lo = (o == 0), hi = min(dim - o, 510) per axis
-  constexpr unsigned GUARD = (1u << 29) | (1u << 19) | (1u << 9);
-  const int h_lds0 = (gt >> 1) * P + (gt & 1) * 16;          // + it * 128 * P
-  constexpr unsigned OOB = 0x7fff0000u;
-  const int w_half = grp == 1 ? 0 : WH;                       // group 1 fills pieces [0, WH), group 0 [WH, 2 WH)
-  // weight piece q = w_half + gt + 256 it = (tap, lane): tap = q >> 6 advances by 4 per `it`, the lane part is a per-thread
-  // constant -- its global offset is rebuilt at every fetch (a handful of VALU on the staging wave; registers are the
-  // scarce thing at two waves per SIMD)
-  const int w_q0 = w_half + gt;
-  const bool wf = p.wfrag != nullptr;                         // fragment-ordered weights: piece q of a chunk image sits at q * 16
-  const unsigned w_lane_b = wf ? (unsigned)((w_q0 & 63) * 16)
-                               : (unsigned)((((n0 + (w_q0 & 31)) * p.C) + ((w_q0 >> 5) & 1) * 8) * 2);
-  const int w_lds0 = w_q0 * 16;                               // + it * 4096
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(xb), 0, p.xbytes, 0x00020000);
-  const bf16_t* wfb = wf ? static_cast<const bf16_t*>(p.wfrag) + (long)b * p.wfrag_sb + (long)blockIdx.y * (nch * 27 * 512) : wb;
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(wfb), 0, wf ? (unsigned)(nch * 27 * 1024) : p.wbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(xb), 0, 0, 0x00020000);   // reads as zero
-
-  // fragment bases: this wave's M-tiles are rows y0, y0 + 1 of plane zq
-  const int zq = wq >> 1, y0w = (wq & 1) * 2;
-  // (LX = 4: M-tile j = 2 wq + i is rows 2 (j & 3), 2 (j & 3) + 1 of plane zq; the lane's voxel is (fr >> 4, fr & 15) in it)
-  const int a_base = LX == 5 ? ((zq * HY + y0w) * HX + fr) * P + fh * 16
-                             : ((zq * HY + y0w * RY + (fr >> LX)) * HX + (fr & (TX - 1))) * P + fh * 16;
-  const int w_frag = lane * 16;
-
-  // ---- this group's tile walk ----
-  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
-  int id_end = id_begin + p.ids_per_block;
-  if (id_end > p.ids_total) id_end = p.ids_total;
-  struct Cur { int valid, cc, tix, tiy, tiz, id; };
-  auto first_tile = [&](Cur& c, int from) {        // first valid id >= from with the group's parity relative to id_begin
-    c.cc = 0; c.valid = 0; c.tix = c.tiy = c.tiz = 0;
-    int id = from;
-    while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, c.tix, c.tiy, c.tiz)) id += 2;
-    c.id = id;
-    c.valid = id < id_end;
-  };
-  auto advance = [&](Cur& c) {
-    if (!c.valid) return;
-    if (c.cc + 1 < nch) { ++c.cc; return; }
-    first_tile(c, c.id + 2);
-  };
-  // tiles of the two groups: count them (the phase count must be the same for every wave of the block)
-  int nt0 = 0, nt1 = 0;
-  {
-    int a, bq, c;
-    for (int id = id_begin; id < id_end; ++id)
-      if (tile_coords(id, p.ntx, p.nty, p.ntz, a, bq, c)) { if ((id - id_begin) & 1) ++nt1; else ++nt0; }
-  }
-  const int nsteps = (nt0 > nt1 ? nt0 : nt1) * nch;
-  if (nsteps == 0) return;
-  const int nphases = 2 * nsteps + 4;                // (a multiple of 4: nch is even) + 1 round: the last tiles are finished in a staging phase
-
-  // (native 4-dword vectors: as HIP uint4 structs the loop-carried pieces were split into scalars, the loads landed in
-  // temporaries and the copies into the carried registers put an s_waitcnt vmcnt(0) in front of every barrier)
-  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-  // Halo pieces are fetched for TWO consecutive chunk steps at once (hreg[0]: the even chunk, hreg[1]: the odd one -- the
-  // two 32-byte halves of a 64-byte run of every voxel row) and written to LDS one step apart: fetched one step at a time,
-  // every 128-byte line went through L1 once per 16-channel chunk (4x the useful bytes at C = 64; staging alone 506 us
-  // for 64 -> 32 at 128^3 next to 325 us of matrix phases).
-  u32x4_t hreg[2][HIT], wreg[WIT];
-  auto load_halo = [&](const Cur& c) {               // c: the even chunk step of a pair
-    const int z0 = c.tiz * TZ, y0 = c.tiy * TY, x0 = c.tix * TX;
-    const int zb = z0 - 1, yb0 = y0 - 1, xb0 = x0 - 1;
-    const unsigned org_b = (unsigned)((((long)(zb * p.H + yb0) * p.W + xb0) * p.ldx + c.cc * 16) * 2);
-    const __amdgpu_buffer_rsrc_t rs = c.valid ? rs_x : rs_0;
-    const unsigned lo = ((unsigned)(z0 == 0) << 20) | ((unsigned)(y0 == 0) << 10) | (unsigned)(x0 == 0);
-    const int hz_ = p.D - z0 < 510 ? p.D - z0 : 510, hy_ = p.H - y0 < 510 ? p.H - y0 : 510, hx_ = p.W - x0 < 510 ? p.W - x0 : 510;
-    const unsigned hi = (((unsigned)hz_ << 20) | ((unsigned)hy_ << 10) | (unsigned)hx_) | GUARD;
-    asm volatile("" : "+v"(h_zyx0));                 // (keeps the per-piece values out of loop-invariant registers)
-    int hz = (int)(h_zyx0 >> 20), hy = (int)((h_zyx0 >> 10) & 1023), hx = (int)(h_zyx0 & 1023);
-#pragma unroll
-    for (int it = 0; it < HIT; ++it) {
-      const unsigned zyx = (gt + 256 * it < HP) ? ((unsigned)hz << 20) | ((unsigned)hy << 10) | (unsigned)hx : 0x1ff7fdffu;   // (invalid: above any limit)
-      const bool ok = ((((zyx | GUARD) - lo) & (hi - zyx)) & GUARD) == GUARD;
-      const unsigned roff = (unsigned)((((hz * p.H + hy) * p.W + hx) * p.ldx + h_half * 8) * 2);
-      const unsigned voff = ok ? org_b + roff : OOB;
-      hx += 128 % HX; hy += 128 / HX;                  // the next piece: 128 rows = 3 x-lines + 26 voxels on (LX = 4: 7 + 2)
-      if (hx >= HX) { hx -= HX; ++hy; }
-      if (hy >= HY) { hy -= HY; ++hz; }
-      hreg[0][it] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-      hreg[1][it] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 32u, 0, 0);  // (OOB + 32 is still out of range)
-    }
-  };
-  auto store_halo = [&](auto odd_c) {
-    constexpr int odd = decltype(odd_c)::value;
-#pragma unroll
-    for (int it = 0; it < HIT; ++it)
-      if (gt + 256 * it < HP) *reinterpret_cast<u32x4_t*>(Hl + h_lds0 + it * 128 * P) = hreg[odd][it];
-  };
-  typedef std::integral_constant<int, 0> even_t;
-  typedef std::integral_constant<int, 1> odd_t;
-  auto load_w = [&](int ws, bool on) {               // this group's half of weight step ws (chunk ws % nch)
-    const int c0_b = wf ? (ws % nch) * (27 * 1024) : (ws % nch) * 32;
-    const __amdgpu_buffer_rsrc_t rs = on ? rs_w : rs_0;
-    const unsigned tap_b = wf ? 1024u : (unsigned)(p.N * p.C * 2);
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      const int tap = (w_q0 >> 6) + 4 * it;
-      const int wt = p.flip ? 26 - tap : tap;
-      const unsigned voff = (gt + 256 * it < WH) ? (unsigned)wt * tap_b + w_lane_b : OOB;
-      wreg[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c0_b, 0);
-    }
-  };
-  auto store_w = [&](int ws) {
-    char* dst = Wl + (ws & 1) * WB + w_lds0;
-#pragma unroll
-    for (int it = 0; it < WIT; ++it)
-      if (gt + 256 * it < WH) *reinterpret_cast<u32x4_t*>(dst + it * 4096) = wreg[it];
-  };
-  auto w_needed = [&](int ws) { return ws < 2 || !w_static; };
-
-  f32x16_t acc[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-  float st_s[4][4], st_q[4][4];
-#pragma unroll
-  for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { st_s[g4][q] = 0.f; st_q[g4][q] = 0.f; }
-  float* const bias_l = reinterpret_cast<float*>(smem + 2 * HB + 2 * WB);      // this block's 32 bias values (read at every tile end)
-  if (tid < 32) bias_l[tid] = p.bias ? p.bias[b * p.bsb + n0 + tid] : 0.f;
-
-  // ---- prologue: weight step 0 complete, group 0's first halo in place, the next loads in flight ----
-  Cur cC, cB, cA;            // computed last / to be stored next / the next PAIR of chunk steps to fetch (cA.cc even)
-  cC.valid = 0; cC.cc = 0; cC.tix = cC.tiy = cC.tiz = 0; cC.id = 0;
-  first_tile(cB, id_begin + grp);
-  cA = cB;
-  auto advance2 = [&](Cur& c) {                      // two chunk steps on (nch is even)
-    if (!c.valid) return;
-    if (c.cc + 2 < nch) { c.cc += 2; return; }
-    first_tile(c, c.id + 2);
-  };
-  load_halo(cA); advance2(cA);                       // steps 0 and 1
-  load_w(0, true);
-  store_w(0);
-  if (grp == 0) {
-    store_halo(even_t{});
-    cC = cB; advance(cB);
-  }
-  load_w(1, w_needed(1));
-  duo_barrier();
-
-  // ================= matrix phase: step ph >> 1 of this group =================
-  auto matrix_phase = [&](int ph) __attribute__((always_inline)) {
-#ifdef COMA_DUO_NO_MFMA          // (diagnostic builds only: profiles/ablate_duo.sh)
-      return;
-#endif
-      if (__builtin_amdgcn_readfirstlane(cC.valid)) {
-        // (readfirstlane: the walk's fields may live in VGPRs, and a vector compare turned this into 32 v_cndmask per phase)
-        if (__builtin_amdgcn_readfirstlane(cC.cc) == 0) {          // a new tile (zeroed here, in place: zeroing in the epilogue made the compiler keep a second copy)
-          asm volatile("" ::: "memory");       // (a real branch: if-converted, this is 32 v_cndmask in every matrix phase)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-        }
-        const char* Wc = Wl + ((ph >> 1) & 1) * WB + w_frag;
-        // xr: LX = 5 the four halo rows y .. y + 3 the wave's two y-neighbour M-tiles share; LX = 4 rows ky + 2 i of the
-        // two M-tiles (each two x-rows high: a tap shift by one row gives different fragments: six reads, rows 0 .. 4)
-        constexpr int NXR = LX == 5 ? 4 : 5;
-        uint4 wg[2][3], xr[2][NXR];
-        auto rdg = [&](int g, int bf) {
-          const int kz = g / 3, kx = g % 3;
-          const int toff = (kz * HY * HX + kx) * P;
-#pragma unroll
-          for (int r = 0; r < NXR; ++r) xr[bf][r] = *reinterpret_cast<const uint4*>(Hl + a_base + toff + r * HX * P);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) wg[bf][ky] = *reinterpret_cast<const uint4*>(Wc + (kz * 9 + ky * 3 + kx) * 1024);
-        };
-        rdg(0, 0);
-#pragma unroll
-        for (int g = 0; g < 9; ++g) {
-          if (g + 1 < 9) rdg(g + 1, (g + 1) & 1);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[i] = mma_piece(wg[g & 1][ky], xr[g & 1][RY * i + ky], acc[i], bf16_t());
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-  };
-  // ================= everything else, for this group's NEXT matrix phase =================
-  // (two forms, chosen at compile time: EVEN writes the even chunk step of a pair and finishes the tile the previous odd step
-  // completed; ODD writes the odd step and fetches the next pair -- a run-time choice put the fetch behind a branch, and
-  // loop-carried pieces behind a branch are copied through temporaries with a vmcnt(0) wait)
-  auto other_phase = [&](auto odd_c, int ph) __attribute__((always_inline)) {
-      constexpr int odd = decltype(odd_c)::value;
-#ifdef COMA_DUO_NO_STAGE
-      if (cC.valid && cC.cc == nch - 1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) asm volatile("" :: "v"(acc[i]));
-      }
-      cC = cB; advance(cB);
-      return;
-#endif
-      store_halo(odd_c);                                // (waits for the pieces fetched two or more phases ago)
-      const int ws = (ph >> 1) + 1;
-      if (w_needed(ws)) store_w(ws);
-      // every piece fetched two phases ago has been consumed (or, masked off, may be dropped): say so -- a piece stored under
-      // a lane mask or a skipped weight refill stays "in flight" for the waitcnt pass, which then drains vmcnt in front of
-      // the next fetch AND at the start of the next matrix phase
-      __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0): free at run time, the pieces are two phases old
-      // finish the tile whose last chunk this group computed in the previous phase
-      if constexpr (odd == 0) {
-#ifdef COMA_DUO_NO_EPI
-      if (cC.valid && cC.cc == nch - 1) {          // (diagnostic: the accumulators stay live, nothing is stored)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) asm volatile("" :: "v"(acc[i]));
-      }
-#else
-      if (cC.valid && cC.cc == nch - 1) {
-        const int x0 = cC.tix * TX, y0 = cC.tiy * TY, z0 = cC.tiz * TZ;
-        float4 bq[4];                                 // this lane's 16 bias values, four LDS reads in flight together
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) bq[g4] = *reinterpret_cast<const float4*>(bias_l + 8 * g4 + 4 * fh);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int j = wq * 2 + i;
-          const int gz = z0 + (j >> 2), gy = y0 + (j & 3) * RY + (fr >> LX), gx = x0 + (fr & (TX - 1));
-          const bool valid = gz < p.D && gy < p.H && gx < p.W;
-          unsigned pk[4][2];
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            bf16_t o[4];
-            const float bv[4] = {bq[g4].x, bq[g4].y, bq[g4].z, bq[g4].w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              o[q] = static_cast<bf16_t>(acc[i][g4 * 4 + q] + bv[q]);
-              if constexpr (STATS) {
-                const float r = valid ? static_cast<float>(o[q]) : 0.f;
-                st_s[g4][q] += r; st_q[g4][q] = fmaf(r, r, st_q[g4][q]);
-              }
-            }
-            const uint2 u = *reinterpret_cast<const uint2*>(o);
-            pk[g4][0] = u.x; pk[g4][1] = u.y;
-          }
-          bf16_t* vox = yb + ((long)(gz * p.H + gy) * p.W + gx) * p.ldy + n0 + 8 * fh;
-#pragma unroll
-          for (int gp = 0; gp < 2; ++gp) {
-            const auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * gp][0], pk[2 * gp + 1][0], false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * gp][1], pk[2 * gp + 1][1], false, false);
-            if (valid) *reinterpret_cast<uint4*>(vox + 16 * gp) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-#endif
-      }
-      // rotate the walk; behind the odd step of a pair, fetch the next pair
-      cC = cB; advance(cB);
-      if constexpr (odd == 1) { load_halo(cA); advance2(cA); }
-      if (w_needed(ws + 1)) load_w(ws + 1, true);
-  };
-  // Two straight-line loops, one per role order (NOT one loop with a role branch: the pieces in flight are loop-carried
-  // registers, and across a branch the compiler parked the loads in temporaries and copied them behind an s_waitcnt
-  // vmcnt(0) -- in front of every barrier).  Both loops execute two barriers per round.
-  // Enter the loops with nothing in flight: the waitcnt pass merges the prologue's pending loads (other registers than the
-  // loop's) into the loop header state and then waits vmcnt(0) wherever the loop body reuses one of those registers --
-  // at the start of every matrix phase.  (The builtin, not inline asm: the pass has to see this wait.)
-  __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) only
-  if (grp == 0) {        // (its first halo was written by the prologue: even step in place, the odd one follows)
-#pragma unroll 1
-    for (int ph = 0; ph < nphases; ph += 4) {
-      matrix_phase(ph); duo_barrier(); other_phase(odd_t{}, ph + 1); duo_barrier();
-      matrix_phase(ph + 2); duo_barrier(); other_phase(even_t{}, ph + 3); duo_barrier();
-    }
-  } else {
-#pragma unroll 1
-    for (int ph = 0; ph < nphases; ph += 4) {
-      other_phase(even_t{}, ph); duo_barrier(); matrix_phase(ph + 1); duo_barrier();
-      other_phase(odd_t{}, ph + 2); duo_barrier(); matrix_phase(ph + 3); duo_barrier();
-    }
-  }
-
-  // ---- fused statistics: lanes -> wave -> block (LDS) -> the caller's record ----
-  if constexpr (STATS) {
-    if (p.stats) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      float* red = reinterpret_cast<float*>(smem);      // [8 waves][32 ch][2]
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float a = st_s[g4][q], c = st_q[g4][q];
-#pragma unroll
-          for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
-          if (fr == 0) { red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2] = a; red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2 + 1] = c; }
-        }
-      __syncthreads();
-      if (tid < 32 && n0 + tid < p.N) {
-        double a = 0.0, c = 0.0;
-        for (int w = 0; w < 8; ++w) { a += (double)red[(w * 32 + tid) * 2]; c += (double)red[(w * 32 + tid) * 2 + 1]; }
-        const int g = p.stats_inst ? b : 0;
-        stat_add(p.stats, p.stats_inst ? p.stats_inst : 1, p.N, g, n0 + tid, a, c);
-      }
     }
   }
 }
@@ -2090,374 +1678,6 @@ static bool pw_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tens
 }
 
 
-// =====================================================================================
-// conv_mfma_tconv_k -- stride-2 3x3x3 TRANSPOSED convolution (the up-convolutions, attn_unet_data_parallel.py:120-131,223)
-// and the data-gradient of the stride-2 encoder convolutions (:318-325), coarse width >= 32, with the COARSE halo staged
-// once per channel chunk in LDS (round 3; these layers ran on conv_mfma_gather_k: every K step re-gathered from global,
-// 3.0x its algorithmic HBM bytes, 8 % of the bf16 peak).
-//   out[2m + p] = sum over taps t with (2m + p + 1 - t) even of x[(2m + p + 1 - t) / 2] w[t], per dimension:
-//     p = 0: tap 1 at x[m];   p = 1: tap 0 at x[m + 1] and tap 2 at x[m]
-// so a coarse tile of 2 x 4 x 32 voxels plus a ONE-voxel halo on the high side of each dimension (3 x 5 x 33 = 495 rows)
-// yields all 8 output-parity classes of its 4 x 8 x 64 fine voxels: 27 (class, tap) pairs = 27 MFMA K-steps per coarse
-// voxel and 32-channel chunk, none of them a zero-stuffed tap.  The pairs are walked by halo offset delta in {0,1}^3: the
-// voxel fragment of a delta is read once and feeds up to 8 pairs -- about one LDS fragment read per MFMA (the stride-1
-// kernel needs 1.5).  The classes are processed in two balanced passes of 4 (13 + 14 pairs; see TC_* below): a wave keeps
-// 4 classes x 2 M-tiles = 128 accumulator registers and each pass streams the channel chunks through one 75 KB LDS image
-// (the pass's 14 weight slots x 32 outputs 35 KB + halo 39 KB), one block per CU.
-// Everything else follows conv_mfma_halo2_k: persistent blocks over XCD-contiguous tile runs, buffer loads with hardware
-// zero fill, the next step's 15 staging pieces issued inside the MFMA loop, 80-byte LDS rows, (weights x voxels)
-// orientation with 16-byte stores, norm statistics out of the epilogue (STATS), COMA_ACCUMULATE.
-// Measured (MI355X, 2 x 64^3 x 64 -> 2 x 128^3 x 32, 58 GFLOP, 335 MB): 139 us = 416 TFLOP/s against 298 us on the gather
-// kernel; 128 -> 64 to 64^3: 51 us = 567 TFLOP/s against 94 us.  The layer is output-heavy (8 fine voxels per coarse one:
-// 256 outputs per lane and tile next to 216 MFMAs) and memory-side bound: PMC of the first version 262 MB written (exact)
-// but 130-260 MB fetched for 67 MB of input (the output stream evicts the halo between the two passes; TCC hit rate 61 %),
-// 41 % of the wave cycles waiting.  Two blocks per CU (a 256-register variant, 12 spilled registers) measured 147 us /
-// 47 us: no gain where it matters, so one block per CU stays.  Next: both channel chunks of a tile's halo resident for its
-// two passes (C = 64: 115 KB), or LDS-DMA staging into a double-buffered image.
-// =====================================================================================
-struct TconvP {
-  const void* x; int ldx; long sbx; int D, H, W, C;      // coarse input
-  void* y; int ldy; long sby; int Do, Ho, Wo, N;         // fine output (<= 2 x coarse per dimension)
-  const void* w; long wsb;                               // [b][27][N][C]
-  const float* bias; int bsb;
-  int ntx, nty, ntz, ids_total, ids_per_block;
-  unsigned xbytes, wbytes;
-  int accum;
-  double2* stats; int stats_inst;
-};
-
-// (TC_NP / TC_DELTA / TC_LCLS / TC_TAP / TC_CLS, the 27 (class, tap) pairs in two passes: conv_tiles.h)
-
-// STATS: the fused norm statistics (forward of the up-convolutions); without them the kernel also takes COMA_ACCUMULATE
-// (data gradients).  Two instantiations because the statistics' 32 accumulators are live across the whole tile loop: the
-// variant without them needs no scratch.
-template <typename T, bool STATS>
-__global__ __launch_bounds__(256, 1) void conv_mfma_tconv_k(TconvP p) {
-  constexpr int EPB = elem<T>::EPB;
-  constexpr bool F32 = EPB == 4;
-  constexpr int CK = 4 * EPB;                          // channels per 64-byte LDS row: 32 bf16 / 16 fp32
-  constexpr int TX = 32, TY = 4, TZ = 2, HX = TX + 1, HY = TY + 1, HZ = TZ + 1, HV = HX * HY * HZ;   // 495 halo rows
-  constexpr int P = 80;                                // LDS row pitch (bytes): conflict-free ds_read_b128 over 16 consecutive rows
-  constexpr int HP = HV * 4, HIT = (HP + 255) / 256;   // 1980 halo pieces of 16 bytes -> 8 per thread
-  constexpr int WS = 14, WP = WS * 32 * 4, WIT = WP / 256;   // 14 weight slots = 1792 pieces -> 7 per thread
-  static_assert(WP % 256 == 0 && HIT + WIT <= 2 * 13, "at most two prefetch pieces per (class, tap) pair");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Wl = smem;                                     // [14 * 32][80]  (first: its fragment offsets then fit the ds_read immediate)
-  char* Hl = smem + WS * 32 * P;                       // [HV][80]
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int b = blockIdx.z, n0 = blockIdx.y * 32;
-  const int fr = lane & 31, fh = lane >> 5;
-  const T* xb = static_cast<const T*>(p.x) + (long)b * p.sbx;
-  const T* wb = static_cast<const T*>(p.w) + (long)b * p.wsb;
-  T* yb = static_cast<T*>(p.y) + (long)b * p.sby;
-  const int nchunks = p.C / CK;
-  constexpr unsigned OOB = 0x7fff0000u;
-
-  // ---- staging descriptors (tile independent).  The layer is output-heavy (8 fine voxels per coarse one): next to 216
-  // MFMAs per tile every VALU instruction counts (first version: 13 VALU per MFMA, 26 % of the wave cycles).  Halo piece:
-  // BYTE offset in x relative to the tile origin; its halo coordinates as three 9-bit fields hz << 20 | hy << 10 | hx, so
-  // that the in-volume test of a piece is ONE subtraction against the packed per-tile limits (guard bits 9 / 19 / 29
-  // survive iff every field is within its limit); its LDS byte offset ----
-  unsigned h_boff[HIT], h_zyx[HIT];
-#pragma unroll
-  for (int it = 0; it < HIT; ++it) {
-    const int piece = tid + 256 * it;
-    const int row = piece >> 2, ch = piece & 3;
-    const int hx = row % HX, hy = (row / HX) % HY, hz = row / (HX * HY);
-    h_boff[it] = (unsigned)((((hz * p.H + hy) * p.W + hx) * p.ldx + ch * EPB) * (int)sizeof(T));
-    h_zyx[it] = piece < HP ? ((unsigned)hz << 20) | ((unsigned)hy << 10) | (unsigned)hx : 0x1ff00000u;      // (invalid: beyond any limit)
-  }
-  const int h_lds0 = (tid >> 2) * P + (tid & 3) * 16;      // piece `it` of this thread: + it * 64 rows (an immediate, not a register)
-  constexpr unsigned GUARD = (1u << 29) | (1u << 19) | (1u << 9);
-  // weight piece `it` of this thread: slot 2 it + (tid >> 7), output row n = (tid >> 2) & 31, 16-byte chunk tid & 3; the
-  // slot's tap differs between the two passes: both byte offsets are kept (OOB = the empty 14th slot of pass A)
-  const int w_s0 = tid >> 7, w_n = (tid >> 2) & 31, w_ch = tid & 3;
-  const int w_lds0 = (w_s0 * 32 + w_n) * P + w_ch * 16;
-  constexpr int W_LSTEP = 2 * 32 * P;
-  // (the 14 byte offsets of a thread's weight pieces are rebuilt at every fetch -- one multiply-add from a compile-time tap
-  // pair -- instead of living in 14 registers: with the statistics the kernel spilled 28)
-  unsigned w_row = (unsigned)(((long)(n0 + w_n) * p.C + w_ch * EPB) * (long)sizeof(T));
-  const unsigned w_tap = (unsigned)((long)p.N * p.C * (long)sizeof(T));         // bytes between two taps
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(xb), 0, p.xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wb), 0, p.wbytes, 0x00020000);
-
-  // fragment read bases: voxel operand = this lane's coarse voxel row in each of the wave's two M-tiles
-  int a_base[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int j = wid * 2 + i;
-    a_base[i] = (((j >> 2) * HY + (j & 3)) * HX + fr) * P + fh * 16;
-  }
-  const int w_base = fr * P + fh * 16;
-
-  typedef unsigned tc_u32x4_t __attribute__((ext_vector_type(4)));      // (native vectors: see conv_mfma_duo_k)
-  tc_u32x4_t hreg[HIT], wreg[WIT];
-  // lim: the tile's packed limits ((D - z0 - 1) << 20 | (H - y0 - 1) << 10 | (W - x0 - 1)) | GUARD, fields clamped to 511
-  auto tile_lim = [&](int z0, int y0, int x0) -> unsigned {
-    const int lz = p.D - z0 - 1 < 511 ? p.D - z0 - 1 : 511, ly = p.H - y0 - 1 < 511 ? p.H - y0 - 1 : 511, lx = p.W - x0 - 1 < 511 ? p.W - x0 - 1 : 511;
-    return ((unsigned)lz << 20) | ((unsigned)ly << 10) | (unsigned)lx | GUARD;
-  };
-  auto halo_piece = [&](const __amdgpu_buffer_rsrc_t& rs, int it, unsigned lim, unsigned org_b) -> tc_u32x4_t {
-    const bool ok = ((lim - h_zyx[it]) & GUARD) == GUARD;
-    const unsigned voff = ok ? org_b + h_boff[it] : OOB;
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-  };
-  // slot 2 it + w_s0 of pass `grp` holds tap TC_TAP[grp][slot] (27 = the empty 14th slot of group A: reads as zero)
-  auto w_piece = [&](const __amdgpu_buffer_rsrc_t& rs, int it, int grp, int c0_b) -> tc_u32x4_t {
-    const int t0 = grp ? TC_TAP[1][2 * it] : TC_TAP[0][2 * it], t1 = grp ? TC_TAP[1][2 * it + 1] : TC_TAP[0][2 * it + 1];
-    const int tap = w_s0 ? t1 : t0;
-    asm volatile("" : "+v"(w_row));                  // (not hoisted back into loop-invariant registers)
-    const unsigned voff = tap < 27 ? w_row + (unsigned)tap * w_tap : OOB;
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, c0_b, 0);
-  };
-  auto tile_org = [&](int z0, int y0, int x0, int c0) -> unsigned {
-    return (unsigned)((((long)(z0 * p.H + y0) * p.W + x0) * p.ldx + c0) * (long)sizeof(T));
-  };
-
-  const int id_begin = xcd_remap(blockIdx.x, gridDim.x) * p.ids_per_block;
-  int id_end = id_begin + p.ids_per_block;
-  if (id_end > p.ids_total) id_end = p.ids_total;
-  int id = id_begin, tix = 0, tiy = 0, tiz = 0;
-  while (id < id_end && !tile_coords(id, p.ntx, p.nty, p.ntz, tix, tiy, tiz)) ++id;
-  if (id >= id_end) return;
-  {
-    const unsigned org = tile_org(tiz * TZ, tiy * TY, tix * TX, 0), lim = tile_lim(tiz * TZ, tiy * TY, tix * TX);
-#pragma unroll
-    for (int it = 0; it < HIT; ++it) hreg[it] = halo_piece(rs_x, it, lim, org);
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) wreg[it] = w_piece(rs_w, it, 0, 0);
-  }
-
-  constexpr bool do_stats = STATS;
-  const bool accum = !STATS && p.accum;
-  float st_s[4][4], st_q[4][4];
-#pragma unroll
-  for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { st_s[g4][q] = 0.f; st_q[g4][q] = 0.f; }
-
-  while (id < id_end) {
-    const int x0 = tix * TX, y0 = tiy * TY, z0 = tiz * TZ;
-    int nid = id + 1, ntix = 0, ntiy = 0, ntiz = 0;
-    while (nid < id_end && !tile_coords(nid, p.ntx, p.nty, p.ntz, ntix, ntiy, ntiz)) ++nid;
-    const bool has_next = nid < id_end;
-
-#pragma unroll
-    for (int grp = 0; grp < 2; ++grp) {
-      f32x16_t acc[4][2];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc[c][i][e] = 0.f;
-
-      for (int cc = 0; cc < nchunks; ++cc) {
-        __syncthreads();                       // all waves finished reading the previous halo / weights
-#pragma unroll
-        for (int it = 0; it < HIT; ++it)
-          if (tid + 256 * it < HP) *reinterpret_cast<tc_u32x4_t*>(Hl + h_lds0 + it * 64 * P) = hreg[it];
-#pragma unroll
-        for (int it = 0; it < WIT; ++it) *reinterpret_cast<tc_u32x4_t*>(Wl + w_lds0 + it * W_LSTEP) = wreg[it];
-        __syncthreads();
-        // what to prefetch while this step computes: the next chunk of this pass, chunk 0 of the tile's second pass, or
-        // chunk 0 / pass A of the next tile; through descriptors whose range is zero when there is nothing left (no branch)
-        const bool same_pass = cc + 1 < nchunks;
-        const bool same_tile = same_pass || grp == 0;
-        const bool pref = same_tile || has_next;
-        const int pz = same_tile ? z0 : ntiz * TZ, py = same_tile ? y0 : ntiy * TY, px = same_tile ? x0 : ntix * TX;
-        const int pc0 = same_pass ? (cc + 1) * CK : 0;
-        const int pgrp = same_pass ? grp : 1 - grp;
-        const __amdgpu_buffer_rsrc_t rs_xp = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(xb), 0, pref ? p.xbytes : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_wp = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(wb), 0, pref ? p.wbytes : 0, 0x00020000);
-        const unsigned porg = tile_org(pz, py, px, pc0), plim = tile_lim(pz, py, px);
-        const int pc0_b = pc0 * (int)sizeof(T);
-
-        uint4 wv[2][2], xv[2][2][2];           // fragments one pair (weights) / one delta (voxels) ahead
-        auto rd_w = [&](int k, int bf) {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) wv[bf][ks] = *reinterpret_cast<const uint4*>(Wl + w_base + k * 32 * P + ks * 32);
-        };
-        auto rd_x = [&](int di, int bf) {
-          const int doff = ((((di >> 2) & 1) * HY + ((di >> 1) & 1)) * HX + (di & 1)) * P;
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) xv[bf][i][ks] = *reinterpret_cast<const uint4*>(Hl + a_base[i] + doff + ks * 32);
-        };
-        rd_x(0, 0);
-        rd_w(0, 0);
-        constexpr int NPMAX = 14;
-#pragma unroll
-        for (int k = 0; k < NPMAX; ++k) {
-          if (k >= TC_NP[grp]) continue;         // (compile time: grp and k are unrolled)
-          const int di = TC_DELTA[grp][k], lc = TC_LCLS[grp][k];
-          if (k + 1 < TC_NP[grp]) {
-            rd_w(k + 1, (k + 1) & 1);
-            if (TC_DELTA[grp][k + 1] != di) rd_x(TC_DELTA[grp][k + 1], TC_DELTA[grp][k + 1] & 1);
-          }
-          // prefetch pieces: 15 per step over 13 / 14 pairs (one per pair, the last ones two)
-          if (k < WIT) wreg[k] = w_piece(rs_wp, k, pgrp, pc0_b);
-          else if (k - WIT < HIT) hreg[k - WIT] = halo_piece(rs_xp, k - WIT, plim, porg);
-          if (k == TC_NP[grp] - 1) {
-#pragma unroll
-            for (int r = TC_NP[grp] - WIT; r < HIT; ++r) hreg[r] = halo_piece(rs_xp, r, plim, porg);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc[lc][i] = mma_piece(wv[k & 1][ks], xv[di & 1][i][ks], acc[lc][i], T());
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      // ---- epilogue of this pass's 4 classes: lane = one coarse voxel of each M-tile, 4 groups of 4 consecutive channels ----
-      const bool has_bias = p.bias != nullptr;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int j = wid * 2 + i;
-        const int cz = z0 + (j >> 2), cy = y0 + (j & 3), cx = x0 + fr;
-        const bool cin = cz < p.D && cy < p.H && cx < p.W;
-        const bool vz1 = 2 * cz + 1 < p.Do, vy1 = 2 * cy + 1 < p.Ho, vx1 = 2 * cx + 1 < p.Wo;      // (odd fine sizes: the last odd plane is absent)
-        const long vbase = ((long)(2 * cz * p.Ho + 2 * cy) * p.Wo + 2 * cx) * p.ldy + n0;         // fine voxel (2cz, 2cy, 2cx)
-#pragma unroll
-        for (int lc = 0; lc < 4; ++lc) {
-          __builtin_amdgcn_sched_barrier(0);     // one class at a time: interleaved, the 8 unrolled instances spill
-          const int cls = TC_CLS[grp][lc];
-          const bool valid = cin && (!(cls & 4) || vz1) && (!(cls & 2) || vy1) && (!(cls & 1) || vx1);
-          const long voff = vbase + ((long)(((cls >> 2) & 1) * p.Ho + ((cls >> 1) & 1)) * p.Wo + (cls & 1)) * p.ldy;   // (scalar class offset)
-          float of[4][4];
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) of[g4][q] = acc[lc][i][g4 * 4 + q];
-          if (has_bias) {                        // (uniform)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) of[g4][q] += p.bias[b * p.bsb + n0 + 8 * g4 + 4 * fh + q];
-          }
-          if constexpr (F32) {
-            float* dst = reinterpret_cast<float*>(yb) + voff + 4 * fh;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-              float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (accum && valid) old = *reinterpret_cast<const float4*>(dst + 8 * g4);
-              const float o[4] = {of[g4][0] + old.x, of[g4][1] + old.y, of[g4][2] + old.z, of[g4][3] + old.w};
-              if (do_stats) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { const float r = valid ? o[q] : 0.f; st_s[g4][q] += r; st_q[g4][q] = fmaf(r, r, st_q[g4][q]); }
-              }
-              if (valid) *reinterpret_cast<float4*>(dst + 8 * g4) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-          } else {
-            // the two half-waves exchange 4-channel groups (v_permlane32_swap): every lane then owns 8 CONSECUTIVE channels
-            // of its voxel per 16-channel half and writes them with one 16-byte store (as conv_mfma_halo2_k)
-            bf16_t* vox = reinterpret_cast<bf16_t*>(yb) + voff + 8 * fh;
-            if (accum) {
-              // y += : what is already there, brought into the accumulators' lane layout -- a lane reads the 8 consecutive
-              // channels it will store (fh = 0: 16 gp + 0..7, fh = 1: 16 gp + 8..15) and the halves swap back the 4-channel
-              // groups that belong to the other one (the inverse of the exchange in front of the store)
-#pragma unroll
-              for (int gp = 0; gp < 2; ++gp) {
-                uint4 u = make_uint4(0, 0, 0, 0);
-                if (valid) u = *reinterpret_cast<const uint4*>(vox + 16 * gp);
-                const auto s0 = __builtin_amdgcn_permlane32_swap(u.x, u.z, false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(u.y, u.w, false, false);
-                const unsigned w0[2] = {s0[0], s1[0]}, w1[2] = {s0[1], s1[1]};       // channel group 2 gp / 2 gp + 1 of this lane
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                  of[2 * gp][2 * h] += __uint_as_float(w0[h] << 16); of[2 * gp][2 * h + 1] += __uint_as_float(w0[h] & 0xffff0000u);
-                  of[2 * gp + 1][2 * h] += __uint_as_float(w1[h] << 16); of[2 * gp + 1][2 * h + 1] += __uint_as_float(w1[h] & 0xffff0000u);
-                }
-              }
-            }
-            unsigned pk[4][2];
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-              bf16_t o[4];
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                o[q] = static_cast<bf16_t>(of[g4][q]);
-                if (do_stats) { const float r = valid ? static_cast<float>(o[q]) : 0.f; st_s[g4][q] += r; st_q[g4][q] = fmaf(r, r, st_q[g4][q]); }
-              }
-              const uint2 u = *reinterpret_cast<const uint2*>(o);
-              pk[g4][0] = u.x; pk[g4][1] = u.y;
-            }
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-              const auto r0 = __builtin_amdgcn_permlane32_swap(pk[2 * gp][0], pk[2 * gp + 1][0], false, false);
-              const auto r1 = __builtin_amdgcn_permlane32_swap(pk[2 * gp][1], pk[2 * gp + 1][1], false, false);
-              if (valid) *reinterpret_cast<uint4*>(vox + 16 * gp) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-            }
-          }
-        }
-      }
-    }
-    id = nid; tix = ntix; tiy = ntiy; tiz = ntiz;
-  }
-  // ---- fused statistics (as conv_mfma_halo2_k) ----
-  if (STATS) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float a = st_s[g4][q], c = st_q[g4][q];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
-        if (fr == 0) { red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2] = a; red[(wid * 32 + 8 * g4 + 4 * fh + q) * 2 + 1] = c; }
-      }
-    __syncthreads();
-    if (tid < 32 && n0 + tid < p.N) {
-      double a = 0.0, c = 0.0;
-      for (int w = 0; w < 4; ++w) { a += (double)red[(w * 32 + tid) * 2]; c += (double)red[(w * 32 + tid) * 2 + 1]; }
-      const int g = p.stats_inst ? b : 0;
-      stat_add(p.stats, p.stats_inst ? p.stats_inst : 1, p.N, g, n0 + tid, a, c);
-    }
-  }
-}
-
-static bool tconv_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
-  if (d->form != 1 || d->stride != 2 || d->ksize != 3 || x->dtype != y->dtype) return false;
-  static const bool off = getenv("COMA_NO_TCONV") != nullptr;      // (A/B measurements against the gather kernel)
-  if (off) return false;
-  const int es = esize(x->dtype), ck = 64 / es;
-  if (x->W < 32 || x->C % ck || y->C % 32) return false;
-  if ((x->ld * es) % 16 || (x->sb * es) % 16 || (y->ld * es) % 16 || (y->sb * es) % 16) return false;
-  if ((x->data && !aligned16(x->data)) || (y->data && !aligned16(y->data))) return false;
-  if (y->D > 2 * x->D || y->H > 2 * x->H || y->W > 2 * x->W || y->D < 2 * x->D - 1 || y->H < 2 * x->H - 1 || y->W < 2 * x->W - 1) return false;
-  return (unsigned long long)t_vox(x) * x->ld * es < 0x7fff0000ull && (long)t_vox(y) * y->ld < (1L << 31);
-}
-
-template <typename T>
-static int conv_mfma_tconv(const coma_conv_desc* d, const coma_tensor* x, const void* wk, const float* bias, const coma_tensor* y,
-                           hipStream_t s, double2* stats, int stats_inst, int* stats_chunks, int accum) {
-  COMA_CHECK(aligned16(wk), "conv_mfma_tconv: weights must be 16-byte aligned");
-  TconvP q;
-  q.x = x->data; q.ldx = (int)x->ld; q.sbx = x->sb; q.D = x->D; q.H = x->H; q.W = x->W; q.C = x->C;
-  q.y = y->data; q.ldy = (int)y->ld; q.sby = y->sb; q.Do = y->D; q.Ho = y->H; q.Wo = y->W; q.N = y->C;
-  q.w = wk; q.wsb = d->per_sample_w ? 27L * y->C * x->C : 0;
-  q.bias = bias; q.bsb = d->per_sample_w ? y->C : 0;
-  q.xbytes = (unsigned)((unsigned long long)t_vox(x) * x->ld * sizeof(T));
-  q.wbytes = (unsigned)(27ull * y->C * x->C * sizeof(T));
-  q.accum = accum;
-  const int nblk_n = y->C / 32;
-  const TileRun r = tile_run(q.D, q.H, q.W, 32, 4, 2, 512, nblk_n * x->B);      // one block per CU, about two rounds
-  q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
-  q.stats = nullptr; q.stats_inst = stats_inst;
-  static const bool fuse_stats = getenv("COMA_TCONV_NO_STATS") == nullptr;      // (A/B: statistics as a separate pass)
-  if (stats && !accum && fuse_stats) { q.stats = stats; *stats_chunks = 1; }
-  const size_t lds = (size_t)(33 * 5 * 3 + 14 * 32) * 80;
-  coma_set_kernel_tag("conv_mfma_tconv_k<%s, %d>", sizeof(T) == 2 ? "__bf16" : "float", q.stats ? 1 : 0);
-  const dim3 grid((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B);
-  if (q.stats) { set_max_lds<conv_mfma_tconv_k<T, true>>(); hipLaunchKernelGGL((conv_mfma_tconv_k<T, true>), grid, dim3(256), lds, s, q); }
-  else { set_max_lds<conv_mfma_tconv_k<T, false>>(); hipLaunchKernelGGL((conv_mfma_tconv_k<T, false>), grid, dim3(256), lds, s, q); }
-  COMA_LAUNCH_CHECK();
-  return 0;
-}
-
 bool conv_mfma_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
   if (x->dtype != COMA_BF16 || y->dtype != COMA_BF16) return false;
   if ((long)t_vox(x) * x->ld >= (1L << 31) || (long)t_vox(y) * y->ld >= (1L << 31)) return false;
@@ -2569,28 +1789,6 @@ static int launch_halo(const HaloP& p0, int B, hipStream_t s) {
   return 0;
 }
 
-// bytes of scratch conv_mfma_duo_k wants for a fragment-ordered copy of the weights (C >= 64 stride-1 3^3 bf16 layers), else 0
-// COMA_NO_DUO=1: conv_mfma_halo2_k everywhere (0); COMA_DUO_C32_ONLY=1: the C == 32 layers only (1); default: all (2)
-static int duo_mode() {
-  static const int mode = getenv("COMA_NO_DUO") != nullptr ? 0 : getenv("COMA_DUO_C32_ONLY") != nullptr ? 1 : 2;
-  return mode;
-}
-static size_t duo_frag_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
-  if (duo_mode() < 2 || x->dtype != COMA_BF16 || d->ksize != 3 || d->stride != 1 || x->W < 16) return 0;
-  if (x->C < 64 || x->C % 16 || y->C % 32) return 0;
-  return (size_t)(d->per_sample_w ? x->B : 1) * 27 * y->C * x->C * 2;
-}
-
-// does conv_mfma_halo<bf16_t> run this problem on conv_mfma_duo_k with fragment-ordered weights (given 16-byte aligned
-// weights)?  Every condition of the dispatch below that does not depend on the weight pointer or the scratch.
-static bool duo_wide_ok(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* y) {
-  if (duo_frag_bytes(d, x, y) == 0 || x->C <= 32 || x->C % 32) return false;
-  const bool vecx = x->ld % 8 == 0 && x->sb % 8 == 0 && aligned16(x->data);
-  const bool st16 = y->ld % 8 == 0 && y->sb % 8 == 0 && aligned16(y->data);
-  return vecx && st16 && (unsigned long long)t_vox(x) * x->ld * sizeof(bf16_t) < 0x7fff0000ull &&
-         x->D <= 510 && x->H <= 510 && x->W <= 510;
-}
-
 // stats != NULL requests fused {sum, sumsq} partials; *stats_chunks receives the number of chunks written, or stays
 // 0 when the selected kernel variant cannot fuse them (the caller then runs the stand-alone statistics pass).
 // wk_frag: wk already holds duo_relayout_k's order (conv_mfma_wk_frag_bytes() > 0 was checked by the caller).
@@ -2650,6 +1848,7 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
     q.stats = nullptr; q.stats_inst = stats_inst;
     q.st8 = y->ld % 4 == 0 && y->sb % 4 == 0 && (((uintptr_t)y->data) & 7) == 0;
     q.st16 = y->ld % EPB == 0 && y->sb % EPB == 0 && (((uintptr_t)y->data) & 15) == 0;
+    q.wfrag = nullptr; q.wfrag_sb = 0;
     const int txv = lx == 5 ? 32 : 16, tyv = lx == 5 ? 4 : 8;      // tile: 2 x 4 x 32 voxels, or 2 x 8 x 16 on the 16-wide grids
     const int nblk_n = (q.N + 31) / 32;
     // thin: 2 blocks per CU, thick: 1; fp32 tiles are 16x longer: one round of one block per CU balances best
@@ -2658,47 +1857,8 @@ static int conv_mfma_halo(const coma_conv_desc* d, const coma_tensor* x, const v
     dim3 grid((unsigned)r.gx, (unsigned)nblk_n, (unsigned)x->B);
     if (stats) { q.stats = stats; *stats_chunks = 1; }
     if constexpr (!F32) {
-      // two 4-wave groups per CU alternating matrix and staging phases (conv_mfma_duo_k): full 32-channel output tiles with
-      // 16-byte stores, 16-channel input chunks
-      // Measured (128^3, batch 2; microbenchmarks, duo / halo2): 32 -> 32 forward 282-315 / 321-339 us.  C >= 64 from the plain
-      // weight layout was SLOWER (64 -> 32 732-757 / 683-704 us: a 16-channel weight piece is 32 bytes of a 128-byte row and the
-      // staging group pulled 4x the useful bytes through L1); with the weights re-laid in fragment order by a 4-us launch
-      // (duo_relayout_k into the caller's scratch, coma_conv_fwd_ws_bytes): 64 -> 32 696 / 691 and 665 / 689 (data gradient),
-      // 64 -> 64 at 64^3 129 / 144 and 134 / 150, 128 -> 64 270 / 273 and 277 / 297, 256 -> 128 at 32^3 117 / 125 and 126 / 134;
-      // step 18.09 -> 17.99 ms.  COMA_NO_DUO=1: conv_mfma_halo2_k everywhere; COMA_DUO_C32_ONLY=1: the C == 32 layers only.
-      const bool no_duo = duo_mode() == 0, duo_all = duo_mode() == 2;
-      q.wfrag = nullptr; q.wfrag_sb = 0;
-      const size_t frag_bytes = duo_frag_bytes(d, x, y);      // C >= 64: scratch for the fragment-ordered copy of the weights
-      const bool wide_ok = duo_all && q.C > 32 && frag_bytes > 0 && (wk_frag || (ws && ws_bytes >= frag_bytes && aligned16(ws)));
-      if (!no_duo && !thin && vec && (q.C == 32 || wide_ok) && q.N % 32 == 0 && q.st16 &&
-          q.D <= 510 && q.H <= 510 && q.W <= 510) {
-        if (q.C > 32 && wk_frag) {
-          q.wfrag = wk; q.wfrag_sb = d->per_sample_w ? 27L * q.N * q.C : 0;
-        } else if (q.C > 32) {
-          const long pieces = (long)(frag_bytes / 16);
-          hipLaunchKernelGGL(duo_relayout_k, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, (const uint4*)wk, (uint4*)ws, q.N, q.C / 8, pieces);
-          COMA_LAUNCH_CHECK();
-          q.wfrag = ws; q.wfrag_sb = d->per_sample_w ? 27L * q.N * q.C : 0;
-        }
-        const TileRun r2 = tile_run(q.D, q.H, q.W, txv, tyv, 2, 256, nblk_n * x->B);      // one 512-thread block per CU, once
-        q.ids_per_block = r2.ids_per_block;
-        const dim3 grid2((unsigned)r2.gx, (unsigned)nblk_n, (unsigned)x->B);
-        if (stats) { q.stats = stats; *stats_chunks = 1; }
-        const size_t lds2 = (size_t)2 * 34 * 6 * 4 * 48 + (size_t)2 * 27 * 64 * 16 + 128;
-#define DUO(ST_, LX_) do { set_max_lds<conv_mfma_duo_k<ST_, LX_>>(); hipLaunchKernelGGL((conv_mfma_duo_k<ST_, LX_>), grid2, dim3(512), lds2, s, q); } while (0)
-        if (lx == 5) {
-          coma_set_kernel_tag("conv_mfma_duo_k<%d, 5>", stats ? 1 : 0);
-          if (stats) DUO(1, 5);
-          else DUO(0, 5);
-        } else {
-          coma_set_kernel_tag("conv_mfma_duo_k<%d, 4>", stats ? 1 : 0);
-          if (stats) DUO(1, 4);
-          else DUO(0, 4);
-        }
-#undef DUO
-        COMA_LAUNCH_CHECK();
-        return 0;
-      }
+      size_t frag_bytes;
+      if (duo_takes(d, x, y, q, thin, vec, wk_frag, ws, ws_bytes, &frag_bytes)) return launch_duo(d, x, q, wk, lx, nblk_n, frag_bytes, ws, wk_frag, s);
     }
     COMA_CHECK(!wk_frag, "conv_mfma: fragment-ordered weights on a problem the wide two-group kernel does not take");
     if (lx == 5) {
@@ -3448,11 +2608,9 @@ static int conv_thin16_wgrad(const coma_conv_desc* d, const coma_tensor* x, cons
   q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
-  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-  q.nrep = replicas ? WGRAD_NREP : 1;
-  q.rep_stride = replicas ? wsz : 0;
-  q.dwk = replicas ? (float*)ws : dwk;
-  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(q.dwk, 0, sizeof(float) * wsz * q.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed);
+  if (!rep.out) return 2;
+  q.dwk = rep.out; q.nrep = rep.nrep; q.rep_stride = rep.rep_stride;
   const int cp = q.C > 8 ? 16 : 8, nb = q.N > 16 ? 2 : 1;
   const int nm = cp == 16 ? 27 : 14;
   size_t lds = (size_t)(34 * 6 * 4 + 2) * cp * 2 + (size_t)256 * nb * 16 * 2;
@@ -3463,7 +2621,7 @@ static int conv_thin16_wgrad(const coma_conv_desc* d, const coma_tensor* x, cons
   else if (nb == 2) hipLaunchKernelGGL((conv_thin16_wgrad_k<8, 2>), grid, dim3(256), lds, s, q);
   else hipLaunchKernelGGL((conv_thin16_wgrad_k<8, 1>), grid, dim3(256), lds, s, q);
   COMA_LAUNCH_CHECK();
-  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+  return wgrad_replicas_done(rep, wsz, dwk, s);
 }
 
 // =====================================================================================
@@ -3859,11 +3017,9 @@ static int conv_thin16f_wgrad(const coma_conv_desc* d, const coma_tensor* x, con
   q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
-  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-  q.nrep = replicas ? WGRAD_NREP : 1;
-  q.rep_stride = replicas ? wsz : 0;
-  q.dwk = replicas ? (float*)ws : dwk;
-  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(q.dwk, 0, sizeof(float) * wsz * q.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed);
+  if (!rep.out) return 2;
+  q.dwk = rep.out; q.nrep = rep.nrep; q.rep_stride = rep.rep_stride;
   const int cp = q.C > 8 ? 16 : q.C > 4 ? 8 : 4, nb = q.N > 16 ? 2 : 1;
   const int nm = (27 + 16 / cp - 1) / (16 / cp);
   size_t lds = (size_t)34 * 6 * 4 * cp * 4 + (size_t)256 * nb * 16 * 4;
@@ -3877,7 +3033,7 @@ static int conv_thin16f_wgrad(const coma_conv_desc* d, const coma_tensor* x, con
   else T16FW(4, 1);
 #undef T16FW
   COMA_LAUNCH_CHECK();
-  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+  return wgrad_replicas_done(rep, wsz, dwk, s);
 }
 
 static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy, float* dwk, void* ws,
@@ -3899,13 +3055,11 @@ static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const
   const TileRun r = tile_run(p.D, p.H, p.W, 32, 4, 2, 512, pairs * x->B);
   p.ntx = r.ntx; p.nty = r.nty; p.ntz = r.ntz; p.tiles_total = r.ids_total; p.tiles_per_block = r.ids_per_block;
   const long taps = (long)d->ksize * d->ksize * d->ksize;
-  p.dwk = dwk; p.wsb = d->per_sample_w ? taps * p.N * p.C : 0;
+  p.wsb = d->per_sample_w ? taps * p.N * p.C : 0;
   const long wsz = taps * p.N * p.C * (d->per_sample_w ? x->B : 1);
-  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-  p.nrep = replicas ? WGRAD_NREP : 1;
-  p.rep_stride = replicas ? wsz : 0;
-  if (replicas) p.dwk = (float*)ws;
-  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(p.dwk, 0, sizeof(float) * wsz * p.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed);
+  if (!rep.out) return 2;
+  p.dwk = rep.out; p.nrep = rep.nrep; p.rep_stride = rep.rep_stride;
   const size_t lds = (size_t)(256 + (d->ksize == 3 ? 816 + 1 : 256)) * 64;   // +1 row: the unused packed column reads one voxel past the halo
   const bool vec = p.vec_n && p.vec_c && p.N % 8 == 0 && p.C % 8 == 0;
   const dim3 grid((unsigned)r.gx, (unsigned)pairs, (unsigned)x->B);
@@ -3919,7 +3073,7 @@ static int conv_mfma_wgrad2(const coma_conv_desc* d, const coma_tensor* x, const
 #undef WG2
 #undef WG2_
   COMA_LAUNCH_CHECK();
-  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+  return wgrad_replicas_done(rep, wsz, dwk, s);
 }
 
 bool conv_mfma_wgrad_supported(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy) {

@@ -385,11 +385,9 @@ int conv_pw_f32_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_
   gx = (q.ntiles + q.tiles_per_block - 1) / q.tiles_per_block;      // (no block without a tile)
   const long wsz1 = (long)q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
-  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-  q.nrep = replicas ? WGRAD_NREP : 1;
-  q.rep_stride = replicas ? wsz : 0;
-  q.dwk = replicas ? (float*)ws : dwk;
-  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(q.dwk, 0, sizeof(float) * wsz * q.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed);
+  if (!rep.out) return 2;
+  q.dwk = rep.out; q.nrep = rep.nrep; q.rep_stride = rep.rep_stride;
   size_t lds = (size_t)2 * tv * (q.C + q.N) * 4;
   if (lds < (size_t)wsz1 * 4) lds = (size_t)wsz1 * 4;
   const dim3 grid((unsigned)gx, (unsigned)x->B);
@@ -402,5 +400,5 @@ int conv_pw_f32_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_
   else PWW(2, 2, 64);
 #undef PWW
   COMA_LAUNCH_CHECK();
-  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+  return wgrad_replicas_done(rep, wsz, dwk, s);
 }

@@ -1315,11 +1315,9 @@ int conv_split_thin_wgrad(const coma_conv_desc* d, const coma_tensor* x, const c
   q.ntx = r.ntx; q.nty = r.nty; q.ntz = r.ntz; q.ids_total = r.ids_total; q.ids_per_block = r.ids_per_block;
   const long wsz1 = 27L * q.N * q.C, wsz = wsz1 * (d->per_sample_w ? x->B : 1);
   q.wsb = d->per_sample_w ? wsz1 : 0;
-  const bool replicas = wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-  q.nrep = replicas ? WGRAD_NREP : 1;
-  q.rep_stride = replicas ? wsz : 0;
-  q.dwk = replicas ? (float*)ws : dwk;
-  if (!(zeroed & (replicas ? COMA_ZEROED_WS : COMA_ZEROED_OUT)) && hipMemsetAsync(q.dwk, 0, sizeof(float) * wsz * q.nrep, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
+  const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed);
+  if (!rep.out) return 2;
+  q.dwk = rep.out; q.nrep = rep.nrep; q.rep_stride = rep.rep_stride;
   const dim3 grid((unsigned)r.gx, 1, (unsigned)x->B);
   coma_set_kernel_tag("conv_split_thin_wgrad_k<%d, %d>", cp, nb);
 #define SPLIT_THINW(CP_, NB_) do { set_max_lds<conv_split_thin_wgrad_k<CP_, NB_>, 80>(); \
@@ -1329,5 +1327,5 @@ int conv_split_thin_wgrad(const coma_conv_desc* d, const coma_tensor* x, const c
   else SPLIT_THINW(8, 1);
 #undef SPLIT_THINW
   COMA_LAUNCH_CHECK();
-  return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+  return wgrad_replicas_done(rep, wsz, dwk, s);
 }

@@ -28,6 +28,27 @@ template <auto KERNEL, int KB = 160> static void set_max_lds() {
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // 8 bf16 = one MFMA A/B fragment
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;  // 32x32 accumulator fragment
 
+// ---- element type of the activations / kernel-layout weights: bf16 (v_mfma_f32_32x32x16_bf16) or fp32
+// (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, 1/16 of the bf16 rate -- the "fp32 mode" of the model,
+// north_star's 1e-3 tolerance path).  Both use the SAME LDS images: a row is 64 bytes = 4 pieces of 16 bytes
+// (32 bf16 or 16 fp32 channels), and the 16-byte fragment a lane reads feeds one bf16 MFMA (K = 16: lane half h holds
+// k = 8h..8h+7) or four fp32 MFMAs (K = 2 each: MFMA m takes channel 4h + m of the piece from lane half h, so the
+// K pair of MFMA m is {m, 4 + m} of the 8 channels the two halves read -- the same for both operands).
+template <typename T> struct elem;
+template <> struct elem<bf16_t> { static constexpr int EPB = 8; };    // elements per 16-byte piece
+template <> struct elem<float> { static constexpr int EPB = 4; };
+
+__device__ __forceinline__ f32x16_t mma_piece(const uint4& a, const uint4& b, f32x16_t acc, bf16_t) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(&a), *reinterpret_cast<const bf16x8_t*>(&b), acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16_t mma_piece(const uint4& a, const uint4& b, f32x16_t acc, float) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
+  return acc;
+}
+
 // fused norm statistics: a block ADDS its {sum, sumsq} of one (group, channel) to the caller's zeroed fp64 record
 // rec[COMA_STAT_REPLICAS][G][N][2] (replica stride rounded up to a 64-byte line) with global_atomic_add_f64; every consumer
 // sums the replicas and derives mean / rstd itself (norm.hip, NormStat).  Replicas: float atomics execute at the memory

@@ -523,13 +523,10 @@ int conv_wgrad_planned(const coma_conv_desc* d, const coma_tensor* x, const coma
   if (x->dtype == COMA_F32) {
     // small outputs (the 1..16-channel layers): hundreds of blocks merging into a few cache lines serialise in the
     // atomic unit -- they merge into WGRAD_NREP replicas in the workspace, summed by one small kernel (as wgrad2 does)
-    const bool replicas = !pl.p.plain && wsz <= WGRAD_REP_MAX_ELEMS && ws && ws_bytes >= sizeof(float) * wsz * WGRAD_NREP;
-    pl.p.nrep = replicas ? WGRAD_NREP : 1;
-    pl.p.rep_stride = replicas ? wsz : 0;
-    if (replicas) {
-      pl.p.dwk = (float*)ws;
-      if (!(zeroed & COMA_ZEROED_WS) && hipMemsetAsync(ws, 0, sizeof(float) * wsz * WGRAD_NREP, s) != hipSuccess) { coma_set_error("wgrad memset failed"); return 2; }
-    }
+    // (dwk itself was cleared above where the kernel needs it: COMA_ZEROED_OUT)
+    const WgradRep rep = wgrad_replicas(wsz, dwk, ws, ws_bytes, s, zeroed | COMA_ZEROED_OUT, !pl.p.plain);
+    if (!rep.out) return 2;
+    pl.p.dwk = rep.out; pl.p.nrep = rep.nrep; pl.p.rep_stride = rep.rep_stride;
     const int taps = d->ksize * d->ksize * d->ksize, tpt = 32 / pl.p.cp, ntiles = (taps + tpt - 1) / tpt;
     const int nt = (ntiles + 3) / 4;                  // tiles per wave: 27 -> 7, 14 -> 4, 7 -> 2, <= 4 -> 1
     coma_set_kernel_tag("conv_f32_wgrad_k<%d, %d>", d->form, nt == 1 ? 1 : nt == 2 ? 2 : nt <= 4 ? 4 : 7);
@@ -539,7 +536,7 @@ int conv_wgrad_planned(const coma_conv_desc* d, const coma_tensor* x, const coma
 #undef F32WL
 #undef F32WL_
     COMA_LAUNCH_CHECK();
-    return replicas ? wgrad_replica_sum((const float*)ws, wsz, dwk, s) : 0;
+    return wgrad_replicas_done(rep, wsz, dwk, s);
   }
   const bool vecall = pl.p.vec_n && pl.p.vec_c && dy->C % 8 == 0 && x->C % 8 == 0;
 #define WL_(TNV, TCV, F, V_) do { set_max_lds<conv_mfma_wgrad_k<TNV, TCV, F, V_>>(); hipLaunchKernelGGL((conv_mfma_wgrad_k<TNV, TCV, F, V_>), pl.grid, dim3(256), pl.lds, s, pl.p); } while (0)

@@ -1,9 +1,9 @@
 # Diagnostic builds of conv_mfma_duo_k (outputs are wrong; never shipped): what a phase costs without the matrix work, without
 # the staging group's work, without the tile epilogue.  Run on the GPU box: bash profiles/ablate_duo.sh
 cd $GRAFT_REPO_ROOT/coma_unet_amd/csrc
-OBJ="api.o conv_direct.o conv_point1.o conv_wgrad.o conv_split.o norm.o gate.o elementwise.o weights.o metrics.o comm.o"
+OBJ=$(python -c "import sys; sys.path.insert(0, '..'); import build; print(' '.join(s.replace('.hip', '.o') for s in build.SOURCES if s != 'conv_duo.hip'))")      # (build.py's list)
 for v in NO_MFMA NO_STAGE NO_EPI; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -DCOMA_DUO_$v -c conv_mfma.hip -o /tmp/cm_$v.o 2>/dev/null &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DCOMA_DUO_$v -c conv_duo.hip -o /tmp/cm_$v.o 2>/dev/null &
 done
 wait
 cd $GRAFT_REPO_ROOT

@@ -991,6 +991,43 @@ DISPATCH_ROWS = [
     (32, 32, 3, 2, False, (8, 8, 16), torch.bfloat16, "conv_mfma_gather_k<32, 0, __bf16>", "conv_mfma_gather_k<32, 1, __bf16>", "conv_mfma_wgrad_k<1, 1, 0, 1>"),
     (128, 128, 3, 1, False, (4, 4, 8), torch.bfloat16, "conv_mfma_gather_k<128, 0, __bf16>", "conv_mfma_gather_k<128, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
     (128, 128, 3, 1, False, (4, 4, 8), torch.float32, "conv_mfma_gather_k<128, 0, float>", "conv_mfma_gather_k<128, 0, float>", "conv_f32_wgrad_k<0, 7>"),
+    # the remaining variants the default dispatch can emit, each at the smallest shape that reaches it (tags as the library
+    # printed them before the kernels moved into one file per family: profiles/conv_family_split.txt)
+    # halo2 with the chunk's taps refetched (C >= 64 where the two-group kernel refuses); the wider pointwise variants
+    (64, 48, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<2, 32, 1, 1, __bf16>", "conv_mfma_halo_k<32, 5, 0, __bf16>", "conv_mfma_wgrad2_k<1, 2, 3, 1>"),
+    (48, 16, 1, 1, False, (8, 16, 32), torch.bfloat16, "conv_mfma_pw_k<3, 1>", "conv_mfma_pw_k<1, 2>", "conv_mfma_wgrad2_k<1, 2, 1, 1>"),
+    (64, 48, 1, 1, False, (8, 16, 32), torch.bfloat16, "conv_mfma_pw_k<4, 2>", "conv_mfma_pw_k<3, 2>", "conv_mfma_wgrad2_k<1, 2, 1, 1>"),
+    # fp32 few-channel layers: 4 and 8 padded channels, one and two output blocks
+    (4, 4, 3, 1, False, (4, 8, 32), torch.float32, "conv_thin16f_k<4, 1>", "conv_thin16f_k<4, 1>", "conv_thin16f_wgrad_k<4, 1>"),
+    (4, 32, 3, 1, False, (4, 8, 32), torch.float32, "conv_thin16f_k<4, 2>", "conv_direct_fwd_k<float, 4, 4>", "conv_thin16f_wgrad_k<4, 2>"),
+    (8, 8, 3, 1, False, (4, 8, 32), torch.float32, "conv_thin16f_k<8, 1>", "conv_thin16f_k<8, 1>", "conv_thin16f_wgrad_k<8, 1>"),
+    (8, 32, 3, 1, False, (4, 8, 32), torch.float32, "conv_thin16f_k<8, 2>", "conv_direct_fwd_k<float, 8, 4>", "conv_f32_wgrad_k<0, 2>"),
+    # the first-generation halo kernel on thin layers (W = 16, W = 8) and on vector-legal 8-wide grids
+    (16, 16, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_halo_k<16, 4, 0, __bf16>", "conv_mfma_halo_k<16, 4, 0, __bf16>", "conv_mfma_wgrad_k<1, 1, 0, 1>"),
+    (16, 16, 3, 1, False, (4, 8, 8), torch.bfloat16, "conv_mfma_halo_k<16, 3, 0, __bf16>", "conv_mfma_halo_k<16, 3, 0, __bf16>", "conv_mfma_wgrad_k<1, 1, 0, 1>"),
+    (32, 48, 3, 1, False, (4, 8, 8), torch.bfloat16, "conv_mfma_halo_k<32, 3, 1, __bf16>", "conv_mfma_halo_k<32, 3, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 1>"),
+    # weight gradients: channel counts that are no multiple of 8 (VEC = 0), and the packed thin variants (PK = 2, 4)
+    (12, 12, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_wgrad2_k<0, 2, 3, 2>"),
+    (4, 4, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_wgrad2_k<0, 2, 3, 4>"),
+    (8, 48, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo2_k<1, 16, 0, 2, __bf16>", "conv_mfma_halo_k<32, 5, 0, __bf16>", "conv_mfma_wgrad2_k<1, 2, 3, 4>"),
+    (20, 20, 3, 1, False, (4, 8, 32), torch.bfloat16, "conv_mfma_halo_k<32, 5, 0, __bf16>", "conv_mfma_halo_k<32, 5, 0, __bf16>", "conv_mfma_wgrad2_k<0, 2, 3, 1>"),
+    (20, 20, 1, 1, False, (8, 16, 32), torch.bfloat16, "conv_direct_fwd_k<__bf16, 4, 4>", "conv_direct_fwd_k<__bf16, 4, 4>", "conv_mfma_wgrad2_k<0, 2, 1, 1>"),
+    (20, 20, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_wgrad_k<1, 1, 0, 0>"),
+    (36, 100, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 0, 0>"),
+    (100, 36, 3, 1, False, (4, 8, 16), torch.bfloat16, "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_halo_k<32, 4, 0, __bf16>", "conv_mfma_wgrad_k<1, 2, 0, 0>"),
+    # fp32 gather variants on small grids; the planned weight gradients of transposed layers (FORM = 1)
+    (32, 32, 3, 2, False, (8, 8, 16), torch.float32, "conv_mfma_gather_k<32, 0, float>", "conv_mfma_gather_k<32, 1, float>", "conv_f32_wgrad_k<0, 7>"),
+    (128, 64, 3, 2, True, (4, 4, 16), torch.float32, "conv_mfma_gather_k<64, 1, float>", "conv_mfma_gather_k<128, 0, float>", "conv_f32_wgrad_k<1, 7>"),
+    (64, 128, 3, 2, True, (4, 4, 16), torch.float32, "conv_mfma_gather_k<128, 1, float>", "conv_mfma_gather_k<64, 0, float>", "conv_f32_wgrad_k<1, 7>"),
+    (64, 32, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_mfma_gather_k<32, 1, __bf16>", "conv_mfma_gather_k<64, 0, __bf16>", "conv_mfma_wgrad_k<1, 2, 1, 1>"),
+    (32, 32, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_mfma_gather_k<32, 1, __bf16>", "conv_mfma_gather_k<32, 0, __bf16>", "conv_mfma_wgrad_k<1, 1, 1, 1>"),
+    (32, 64, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_mfma_gather_k<64, 1, __bf16>", "conv_mfma_gather_k<32, 0, __bf16>", "conv_mfma_wgrad_k<2, 1, 1, 1>"),
+    (36, 100, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_direct_fwd_k<__bf16, 4, 4>", "conv_direct_fwd_k<__bf16, 4, 4>", "conv_mfma_wgrad_k<2, 1, 1, 0>"),
+    (100, 36, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_direct_fwd_k<__bf16, 4, 4>", "conv_direct_fwd_k<__bf16, 4, 4>", "conv_mfma_wgrad_k<1, 2, 1, 0>"),
+    (20, 20, 3, 2, True, (4, 4, 16), torch.bfloat16, "conv_direct_fwd_k<__bf16, 4, 4>", "conv_direct_fwd_k<__bf16, 4, 4>", "conv_mfma_wgrad_k<1, 1, 1, 0>"),
+    (4, 4, 3, 2, True, (4, 4, 16), torch.float32, "conv_direct_fwd_k<float, 4, 4>", "conv_direct_fwd_k<float, 4, 4>", "conv_f32_wgrad_k<1, 1>"),
+    (8, 8, 3, 2, True, (4, 4, 16), torch.float32, "conv_direct_fwd_k<float, 8, 4>", "conv_direct_fwd_k<float, 8, 4>", "conv_f32_wgrad_k<1, 2>"),
+    (16, 16, 3, 2, True, (4, 4, 16), torch.float32, "conv_direct_fwd_k<float, 16, 4>", "conv_direct_fwd_k<float, 16, 4>", "conv_f32_wgrad_k<1, 4>"),
 ]
 
 
