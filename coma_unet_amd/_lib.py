@@ -71,6 +71,7 @@ SIGNATURES = {
     "coma_norm_stats": (_i32, [_TP, _i32, _vp, _vp]),
     "coma_norm_act_fwd": (_i32, [_TP, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _TP, _vp]),
     "coma_norm_act_bwd": (_i32, [_TP, _TP, _i32, _vp, _f32, _vp, _vp, _i32, _vp, _TP, _vp, _vp, _vp, _vp, _vp]),
+    "coma_norm_act_bwd_frozen": (_i32, [_TP, _TP, _vp, _vp, _vp, _vp, _i32, _vp, _TP, _vp, _vp, _vp, _vp, _vp]),
     "coma_add_relu_fwd": (_i32, [_TP, _TP, _TP, _vp]),
     "coma_add_relu_bwd": (_i32, [_TP, _TP, _TP, _vp]),
     "coma_gate_mul_fwd": (_i32, [_TP, _TP, _TP, _vp]),
@@ -82,6 +83,10 @@ SIGNATURES = {
     "coma_gate_mid_bwd": (_i32, [_TP, _TP, _TP, _TP, _TP, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _f32, _vp, _vp, _vp,
                                  _TP, _TP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "coma_gate_eval_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _vp, _vp, _vp, _TP, _TP, _vp]),
+    "coma_gate_frozen_ok": (_i32, [_TP, _TP, _TP, _TP]),
+    "coma_gate_frozen_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _vp, _vp, _vp, _TP, _TP, _vp]),
+    "coma_gate_frozen_bwd": (_i32, [_TP, _TP, _TP, _TP, _TP, _vp, _vp, _vp, _vp, _vp, _TP, _i32, _TP, _TP, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "coma_gate_eval_mfma_ok": (_i32, [_TP, _TP, _i32]),
     "coma_gate_eval_mfma": (_i32, [_TP, _TP, _vp, _vp, _vp, _vp, _vp, _TP, _TP, _vp]),
     "coma_add": (_i32, [_TP, _TP, _TP, _vp]),

@@ -30,7 +30,7 @@ from . import _lib as L
 from . import ops
 from ._lib import lib, ct, check
 from .layers import (Config, Convolution, MonaiConvBlock, CondConvolution, CondConvBlock, norm_act, conv_plain,
-                     conv_then_bn, reset_cov_cache, cov_rows, _norm_params)
+                     conv_then_bn, reset_cov_cache, cov_rows, _norm_params, bn_frozen, frozen_stats)
 from .ops import Out
 from .roi_tables import ROI_INDICES, ROI_NAMES, ROI_INDEX_TO_NAME
 from .metrics import RoiCorrMetric, calc_roi_metrics          # noqa: F401  (:36-96, :1361-1397 of the reference module)
@@ -62,6 +62,10 @@ def _padded_input(x, dtype):
     return xi
 
 
+def _refresh_after_load(module, _incompatible_keys):
+    module.refresh_frozen_batchnorm()
+
+
 class UpBlock(nn.Module):
     """attn_unet_data_parallel.py:120-131 (conditional branch)."""
 
@@ -89,7 +93,9 @@ class ObservableAttentionBlock(nn.Module):
 
     def forward(self, g, x, out=None):
         cfg = self.cfg
-        if self.training and cfg.fused_gate:
+        # a gate with a frozen BatchNorm (layers.bn_frozen) takes the piecewise path below, which decides per BatchNorm
+        frozen = self.training and any(bn_frozen(cfg, m) for m in (self.W_g[1], self.W_x[1], self.psi[1]))
+        if self.training and cfg.fused_gate and not frozen:
             # W_g / W_x: MFMA 1x1x1 convolutions with their BatchNorm statistics out of the epilogue; everything behind them
             # (two BatchNorm applies, add, ReLU, psi dot product, its BatchNorm statistics, sigmoid, multiply) is two launches
             # forward and three backward (ops.GateFused, csrc/gate.hip)
@@ -112,8 +118,29 @@ class ObservableAttentionBlock(nn.Module):
             if self.save_attn:
                 return att, psi
             return att
-        g1 = conv_then_bn(cfg, g, self.W_g[0], self.W_g[1], L.ACT_NONE, self.training)
-        x1 = conv_then_bn(cfg, x, self.W_x[0], self.W_x[1], L.ACT_NONE, self.training)
+        g1 = x1 = None
+        if frozen and cfg.fused_gate and all(bn_frozen(cfg, m) for m in (self.W_g[1], self.W_x[1], self.psi[1])):
+            # all three BatchNorms frozen: plain W_g / W_x convolutions (biases, no statistics epilogue), then one launch
+            # forward and one pass + finalise backward (ops.GateFrozen); outside the kernels' envelope the pieces below
+            # take the two raw products
+            g1raw = conv_plain(cfg, g, self.W_g[0].conv, 1, 1, False)
+            x1raw = conv_plain(cfg, x, self.W_x[0].conv, 1, 1, False)
+            if ops.gate_frozen_ok(x, g1raw, x1raw, out if out is not None else x):
+                gg, bg = self.W_g[1].weight, self.W_g[1].bias
+                gx, bx = self.W_x[1].weight, self.W_x[1].bias
+                gp, bp = self.psi[1].weight, self.psi[1].bias
+                pc = self.psi[0].conv
+                stats = (frozen_stats(self.W_g[1]), frozen_stats(self.W_x[1]), frozen_stats(self.psi[1]))
+                att, psi = ops.GateFrozen.apply(x, g1raw, x1raw, gg, bg, gx, bx, pc.weight, pc.bias, gp, bp, stats,
+                                                Out(out) if out is not None else None)
+                if self.save_attn:
+                    return att, psi
+                return att
+            g1 = norm_act(cfg, g1raw, self.W_g[1], L.NORM_BATCH, L.ACT_NONE, None, True)
+            x1 = norm_act(cfg, x1raw, self.W_x[1], L.NORM_BATCH, L.ACT_NONE, None, True)
+        if g1 is None:
+            g1 = conv_then_bn(cfg, g, self.W_g[0], self.W_g[1], L.ACT_NONE, self.training)
+            x1 = conv_then_bn(cfg, x, self.W_x[0], self.W_x[1], L.ACT_NONE, self.training)
         s = ops.AddRelu.apply(g1, x1)
         psi = conv_then_bn(cfg, s, self.psi[0], self.psi[1], L.ACT_SIGMOID, self.training)
         att = ops.GateMul.apply(x, psi, Out(out) if out is not None else None)
@@ -205,6 +232,33 @@ class ObservableAttentionUnet(nn.Module):
                                   up_kernel_size=up_kernel_size, strides=st[0], num_covars=6)
 
         self.model = nn.ModuleList([head, _create_block(self.channels, self.strides), reduce_channels])
+
+    def batchnorms(self):
+        """Every nn.BatchNorm3d holder of the model (cached: the module tree is fixed after construction)."""
+        bns = self.__dict__.get("_bn_list")
+        if bns is None:
+            bns = self.__dict__["_bn_list"] = [m for m in self.modules() if isinstance(m, nn.BatchNorm3d)]
+        return bns
+
+    def freeze_batchnorm(self, on=True):
+        """Frozen-BatchNorm training: while the model is in train mode every BatchNorm3d normalises with its running
+        statistics and writes neither them nor its step counter (fine-tuning a resumed checkpoint at a batch size whose
+        own statistics are noise).  Sticky: survives ``train()`` / ``eval()``; the per-module torch idiom (BatchNorm3d
+        holders in eval mode inside a train-mode model) is honoured as well.  Calling it again re-reads the running
+        statistics into the per-BatchNorm (mean, rstd) tables in place.  InstanceNorm layers are untouched."""
+        for c in (self.cfg, getattr(self, "cfg_heads", None)):
+            if c is not None:
+                c.frozen_bn = bool(on)
+        if on:
+            self.refresh_frozen_batchnorm(every=True)
+        return self
+
+    def refresh_frozen_batchnorm(self, every=False):
+        """Re-derive the (mean, rstd) tables of the frozen BatchNorms from the running buffers, in place (a captured step
+        keeps reading the same addresses).  every=False: only the tables that exist."""
+        for m in self.batchnorms():
+            if (every or "_coma_frozen" in m.__dict__) and m.running_mean is not None and m.running_mean.is_cuda:
+                frozen_stats(m, refresh=True)
 
     def set_save_attn(self, v):
         self.save_attn = v
@@ -313,6 +367,8 @@ class ContrastiveAttentionUNET_DP(ObservableAttentionUnet):
         self.with_uq = kwargs.get("with_uq", False)
         self.static_prompts = kwargs.get("static_prompts", False)
         self.register_buffer("_roi_ids", torch.tensor(self.roi_indices, dtype=torch.int32), persistent=False)
+        # the frozen BatchNorms' (mean, rstd) tables follow a later load_state_dict
+        self.register_load_state_dict_post_hook(_refresh_after_load)
 
     def set_training(self, mode):
         self.training = mode
@@ -373,7 +429,10 @@ class ContrastiveAttentionUNET_DP(ObservableAttentionUnet):
         # a configuration records which layers prepare what)
         if covariate is not None and covariate.dim() == 3 and x.is_cuda:
             ops.PrepAhead.begin(self, (tuple(x.shape), x.dtype, self.cfg.compute_dtype, self.training, torch.is_grad_enabled(),
-                                       bool(x.requires_grad), self.static_prompts, bool(self.cfg.eval_fused)), x.device, covariate, x.shape[0])
+                                       bool(x.requires_grad), self.static_prompts, bool(self.cfg.eval_fused),
+                                       # frozen gates run piecewise (one more prepared layer each): their own plans
+                                       self.training and (self.cfg.frozen_bn or sum(not m.training for m in self.batchnorms()))),
+                                 x.device, covariate, x.shape[0])
         ok = False
         try:
             res = self._forward(x, xi, covariate, roi_pred_dicts, sample_roi_mask)

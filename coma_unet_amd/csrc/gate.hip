@@ -620,13 +620,13 @@ struct GateEvalP {
   const void *wg, *wx;                     // MFMA: folded bf16 weights [32][C], zero rows beyond F
 };
 
+// The pass of a gate whose BatchNorms are affine maps, behind the block's folded LDS tables (scale_g, scale_x, shift, w_psi)
+// and {a_p, b_p}: shared by the eval gate and the frozen gate's forward.
 // `cv` = max(C, F) / VEC lanes per voxel; the lanes with c0 < F form the dot product, those with c0 < C the multiply
 template <typename T, int VEC>
-__global__ __launch_bounds__(256) void gate_eval_fwd_k(GateEvalP p) {
-  __shared__ float t_scg[GATE_TAB], t_scx[GATE_TAB], t_sh[GATE_TAB], t_w[GATE_TAB];
+__device__ __forceinline__ void gate_affine_fwd(const GateEvalP& p, const float* t_scg, const float* t_scx, const float* t_sh,
+                                                const float* t_w, const float pa, const float pb) {
   const int b = blockIdx.y, tid = threadIdx.x;
-  for (int c = tid; c < p.F; c += 256) { t_scg[c] = p.scg[c]; t_scx[c] = p.scx[c]; t_sh[c] = p.sh[c]; t_w[c] = p.w[c]; }
-  __syncthreads();
   const int cv = p.cv;                                   // a power of two <= 64
   const int c0 = (tid % cv) * VEC;
   const bool in_f = c0 < p.F, in_c = c0 < p.C;           // (F and C are multiples of VEC)
@@ -636,7 +636,6 @@ __global__ __launch_bounds__(256) void gate_eval_fwd_k(GateEvalP p) {
     scg[j] = in_f ? t_scg[c0 + j] : 0.f; scx[j] = in_f ? t_scx[c0 + j] : 0.f;
     sh[j] = in_f ? t_sh[c0 + j] : 0.f; w[j] = in_f ? t_w[c0 + j] : 0.f;
   }
-  const float pa = p.ab[0], pb = p.ab[1];
   const T* gb = reinterpret_cast<const T*>(p.g1) + (int64_t)b * p.sbg;
   const T* x1b = reinterpret_cast<const T*>(p.x1) + (int64_t)b * p.sbx1;
   const T* xb = reinterpret_cast<const T*>(p.x) + (int64_t)b * p.sbx;
@@ -681,6 +680,14 @@ __global__ __launch_bounds__(256) void gate_eval_fwd_k(GateEvalP p) {
       }
     }
   }
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gate_eval_fwd_k(GateEvalP p) {
+  __shared__ float t_scg[GATE_TAB], t_scx[GATE_TAB], t_sh[GATE_TAB], t_w[GATE_TAB];
+  for (int c = threadIdx.x; c < p.F; c += 256) { t_scg[c] = p.scg[c]; t_scx[c] = p.scx[c]; t_sh[c] = p.sh[c]; t_w[c] = p.w[c]; }
+  __syncthreads();
+  gate_affine_fwd<T, VEC>(p, t_scg, t_scx, t_sh, t_w, p.ab[0], p.ab[1]);
 }
 
 // The whole gate in one launch, modelled on conv_mfma_pw_k (conv_mfma.hip): no LDS; the folded weights diag(scale) W of both
@@ -840,6 +847,282 @@ extern "C" int coma_gate_eval_mfma(const coma_tensor* g, const coma_tensor* x, c
   else if (ks == 2) hipLaunchKernelGGL((gate_eval_mfma_k<2>), grid, dim3(256), 0, s, p);
   else if (ks == 3) hipLaunchKernelGGL((gate_eval_mfma_k<3>), grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL((gate_eval_mfma_k<4>), grid, dim3(256), 0, s, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// FROZEN gate: a train-mode model whose three gate BatchNorms normalise with their running statistics.  Each is a known
+// affine map (m = running_mean, r = rsqrt(running_var + eps): the caller's fp32 tables), so forward is the eval pass and
+// backward needs no statistics of its own gradients:
+//     t = gam_g ghat + bet_g + gam_x x1hat + bet_x     s = relu(t)     pr = w_psi . s + b_psi
+//     zhat = (pr - m_p) r_p     psi = sigmoid(gam_p zhat + bet_p)      att = x psi
+//   gate_frozen_fwd_k   g1raw, x1raw, x -> att, psi.  s is NOT saved: the backward reads g1raw / x1raw anyway (ghat and
+//                       x1hat for dgamma_g / dgamma_x) and t, s, pr come out of them in registers.
+//   gate_frozen_bwd_k   x, psi, d(att), g1raw, x1raw -> dx (= or +=), dg1raw, dx1raw and the block's sums
+//                       {sum d, sum d ghat, sum d x1hat, sum dpr s}[F], {sum dzp, sum dzp zhat} into a replica record
+//   gate_frozen_finalize_k   record -> the eight parameter gradients and d(b_psi) (one block)
+struct GateFrozenP {
+  GateEvalP e;                             // x, g1raw, x1raw, att (forward), psi, V, B, C, F, cv
+  const float *mean_g, *rstd_g, *gam_g, *bet_g, *mean_x, *rstd_x, *gam_x, *bet_x, *mean_p, *rstd_p, *gam_p, *bet_p;
+  const float *w, *bias;                   // psi convolution: w[F], bias[1] or NULL
+  const void* dout; int64_t ldo, sbo;      // backward: d(att)
+  void* dx; int64_t lddx, sbdx; int acc;   // dx (=) or (+=) d(att) psi
+  void* dg1; int64_t lddg, sbdg;
+  void* dx1; int64_t lddx1, sbdx1;
+  double* rec; int64_t rrs;                // zeroed record [rep][F + 1][4]: [c][4] as above, [F][0..1] the two psi sums
+  float *dgam_g, *dbet_g, *dgam_x, *dbet_x, *dw, *db, *dgam_p, *dbet_p;
+};
+
+// the block's folded tables (whole block; ends with a barrier)
+__device__ __forceinline__ void gate_frozen_fold(const GateFrozenP& p, float* t_scg, float* t_scx, float* t_sh, float* t_w) {
+  for (int c = threadIdx.x; c < p.e.F; c += 256) {
+    const float sg = p.rstd_g[c] * p.gam_g[c], sx = p.rstd_x[c] * p.gam_x[c];
+    t_scg[c] = sg; t_scx[c] = sx;
+    t_sh[c] = (p.bet_g[c] - p.mean_g[c] * sg) + (p.bet_x[c] - p.mean_x[c] * sx);
+    t_w[c] = p.w[c];
+  }
+  __syncthreads();
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gate_frozen_fwd_k(GateFrozenP p) {
+  __shared__ float t_scg[GATE_TAB], t_scx[GATE_TAB], t_sh[GATE_TAB], t_w[GATE_TAB];
+  gate_frozen_fold(p, t_scg, t_scx, t_sh, t_w);
+  // gam_p zhat + bet_p = a_p dot + b_p with a_p = gam_p r_p, b_p = a_p (b_psi - m_p) + bet_p
+  const float pa = p.gam_p[0] * p.rstd_p[0];
+  const float pb = fmaf(pa, (p.bias ? *p.bias : 0.f) - p.mean_p[0], p.bet_p[0]);
+  gate_affine_fwd<T, VEC>(p.e, t_scg, t_scx, t_sh, t_w, pa, pb);
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void gate_frozen_bwd_k(GateFrozenP p) {
+  __shared__ float t_scg[GATE_TAB], t_scx[GATE_TAB], t_sh[GATE_TAB], t_w[GATE_TAB];
+  __shared__ double sh[256][4 * VEC];
+  __shared__ double red[2][4];
+  gate_frozen_fold(p, t_scg, t_scx, t_sh, t_w);
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int cv = p.e.cv;                                 // lanes per voxel: a power of two <= 64
+  const int c0 = (tid % cv) * VEC;
+  const bool in_f = c0 < p.e.F, in_c = c0 < p.e.C;       // (F and C are multiples of VEC)
+  float scg[VEC], scx[VEC], shf[VEC], w[VEC], mg[VEC], rg[VEC], mx[VEC], rx[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    scg[j] = in_f ? t_scg[c0 + j] : 0.f; scx[j] = in_f ? t_scx[c0 + j] : 0.f;
+    shf[j] = in_f ? t_sh[c0 + j] : 0.f; w[j] = in_f ? t_w[c0 + j] : 0.f;
+    mg[j] = in_f ? p.mean_g[c0 + j] : 0.f; rg[j] = in_f ? p.rstd_g[c0 + j] : 0.f;
+    mx[j] = in_f ? p.mean_x[c0 + j] : 0.f; rx[j] = in_f ? p.rstd_x[c0 + j] : 0.f;
+  }
+  const float rp = p.rstd_p[0], cp = p.gam_p[0] * rp;
+  const float zb = ((p.bias ? *p.bias : 0.f) - p.mean_p[0]) * rp;            // zhat = dot r_p + zb
+  const T* gb = reinterpret_cast<const T*>(p.e.g1) + (int64_t)b * p.e.sbg;
+  const T* x1b = reinterpret_cast<const T*>(p.e.x1) + (int64_t)b * p.e.sbx1;
+  const T* xb = reinterpret_cast<const T*>(p.e.x) + (int64_t)b * p.e.sbx;
+  const T* qb = reinterpret_cast<const T*>(p.e.psi) + (int64_t)b * p.e.sbq;
+  const T* ob = reinterpret_cast<const T*>(p.dout) + (int64_t)b * p.sbo;
+  T* dxb = reinterpret_cast<T*>(p.dx) + (int64_t)b * p.sbdx;
+  T* dgb = reinterpret_cast<T*>(p.dg1) + (int64_t)b * p.sbdg;
+  T* dx1b = reinterpret_cast<T*>(p.dx1) + (int64_t)b * p.sbdx1;
+  const int vpb = 256 / cv;                              // voxels per block step
+  const int64_t vstep = (int64_t)gridDim.x * vpb;
+  float f[4 * VEC], f1 = 0.f, f2 = 0.f;
+  double acc[4 * VEC], s1 = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4 * VEC; ++j) { f[j] = 0.f; acc[j] = 0.0; }
+  int cnt = 0;
+  constexpr int U = 2;
+  for (int64_t v = (int64_t)blockIdx.x * vpb + tid / cv; v < p.e.V; v += U * vstep) {   // (whole waves run every trip: shuffles)
+    float gv[U][VEC], x1v[U][VEC], xv[U][VEC], dv[U][VEC], ov[U][VEC], ps[U];
+    bool live[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t vv = v + u * vstep;
+      live[u] = vv < p.e.V;
+      const int64_t va = live[u] ? vv : v;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) { gv[u][j] = 0.f; x1v[u][j] = 0.f; xv[u][j] = 0.f; dv[u][j] = 0.f; ov[u][j] = 0.f; }
+      if (in_f) { vec_io<T, VEC>::load(gb + va * p.e.ldg + c0, gv[u]); vec_io<T, VEC>::load(x1b + va * p.e.ldx1 + c0, x1v[u]); }
+      if (in_c) {
+        vec_io<T, VEC>::load(xb + va * p.e.ldx + c0, xv[u]);
+        vec_io<T, VEC>::load(ob + va * p.ldo + c0, dv[u]);
+        if (p.acc) vec_io<T, VEC>::load(dxb + va * p.lddx + c0, ov[u]);
+      }
+      ps[u] = ld_f(qb + va * p.e.ldq);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t vv = v + u * vstep;
+      float tv[VEC], dot_s = 0.f, dot_x = 0.f;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        tv[j] = fmaf(gv[u][j], scg[j], fmaf(x1v[u][j], scx[j], shf[j]));
+        dot_s = fmaf(tv[j] > 0.f ? tv[j] : 0.f, w[j], dot_s);
+        dot_x = fmaf(xv[u][j], dv[u][j], dot_x);
+        ov[u][j] += dv[u][j] * ps[u];
+      }
+      if (live[u] && in_c) vec_io<T, VEC>::store(dxb + vv * p.lddx + c0, ov[u]);
+      for (int o = cv >> 1; o > 0; o >>= 1) { dot_s += __shfl_xor(dot_s, o, 64); dot_x += __shfl_xor(dot_x, o, 64); }
+      const float dzp = live[u] ? dot_x * ps[u] * (1.f - ps[u]) : 0.f;
+      const float dpr = dzp * cp;
+      if (c0 == 0) { f1 += dzp; f2 = fmaf(dzp, fmaf(dot_s, rp, zb), f2); }
+      float og[VEC], ox[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float d = tv[j] > 0.f ? dpr * w[j] : 0.f;
+        og[j] = d * scg[j]; ox[j] = d * scx[j];
+        f[4 * j] += d;
+        f[4 * j + 1] = fmaf(d, (gv[u][j] - mg[j]) * rg[j], f[4 * j + 1]);
+        f[4 * j + 2] = fmaf(d, (x1v[u][j] - mx[j]) * rx[j], f[4 * j + 2]);
+        f[4 * j + 3] = fmaf(dpr, tv[j] > 0.f ? tv[j] : 0.f, f[4 * j + 3]);
+      }
+      if (live[u] && in_f) {
+        vec_io<T, VEC>::store(dgb + vv * p.lddg + c0, og);
+        vec_io<T, VEC>::store(dx1b + vv * p.lddx1 + c0, ox);
+      }
+    }
+    if (++cnt == 8) {                                    // fp32 partial sums over 16 voxels, folded into fp64
+#pragma unroll
+      for (int j = 0; j < 4 * VEC; ++j) { acc[j] += (double)f[j]; f[j] = 0.f; }
+      s1 += (double)f1; s2 += (double)f2; f1 = 0.f; f2 = 0.f; cnt = 0;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4 * VEC; ++j) sh[tid][j] = acc[j] + (double)f[j];
+  s1 += (double)f1; s2 += (double)f2;
+  s1 = wave_sum(s1); s2 = wave_sum(s2);
+  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
+  __syncthreads();
+  for (int off = vpb >> 1; off > 0; off >>= 1) {         // tree over the block's voxel slots (tid = slot * cv + lane)
+    if (tid / cv < off) {
+#pragma unroll
+      for (int j = 0; j < 4 * VEC; ++j) sh[tid][j] += sh[tid + off * cv][j];
+    }
+    __syncthreads();
+  }
+  // slot 0 of the tree = a contiguous [max(C, F)][4] image; its first F rows are the record's
+  rec_add(p.rec, p.rrs, 0, &sh[0][0], p.e.F * 4);
+  if (tid < 2) {
+    const double t = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    add_f64(p.rec + (int64_t)(blockIdx.x & (COMA_STAT_REPLICAS - 1)) * p.rrs + 4 * p.e.F + tid, t);
+  }
+}
+
+__global__ __launch_bounds__(256) void gate_frozen_finalize_k(GateFrozenP p) {
+  for (int c = threadIdx.x; c < p.e.F; c += 256) {
+    const double a = rec_get(p.rec, p.rrs, 4 * c);
+    if (p.dbet_g) p.dbet_g[c] = (float)a;
+    if (p.dbet_x) p.dbet_x[c] = (float)a;
+    if (p.dgam_g) p.dgam_g[c] = (float)rec_get(p.rec, p.rrs, 4 * c + 1);
+    if (p.dgam_x) p.dgam_x[c] = (float)rec_get(p.rec, p.rrs, 4 * c + 2);
+    if (p.dw) p.dw[c] = (float)rec_get(p.rec, p.rrs, 4 * c + 3);
+  }
+  if (threadIdx.x == 0) {
+    const double sz = rec_get(p.rec, p.rrs, 4 * p.e.F);
+    if (p.dbet_p) p.dbet_p[0] = (float)sz;
+    if (p.dgam_p) p.dgam_p[0] = (float)rec_get(p.rec, p.rrs, 4 * p.e.F + 1);
+    if (p.db) p.db[0] = (float)(sz * (double)(p.gam_p[0] * p.rstd_p[0]));      // sum dpr = gam_p r_p sum dzp
+  }
+}
+
+// vector width and lanes per voxel of the frozen gate kernels over the given tensors (0: outside the envelope)
+static int gate_frozen_vec(int dtype, const coma_tensor* const* ts, int n, int C, int F, int want) {
+  const int m = C > F ? C : F;
+  int vec = gate_vec(ts, n, want);
+  if (vec == 2) vec = 1;
+  while (vec > 1 && !pow2_le64(m / vec)) vec = vec == 8 ? 4 : 1;
+  (void)dtype;
+  return (C % vec == 0 && F % vec == 0 && pow2_le64(m / vec) && F >= 1 && F <= GATE_TAB) ? vec : 0;
+}
+
+static int gate_frozen_common(GateFrozenP& p, const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                              const coma_tensor* psi, const float* const* bn_g, const float* const* bn_x,
+                              const float* const* bn_p, const float* w_psi, const float* b_psi) {
+  p.e.x = x->data; p.e.ldx = x->ld; p.e.sbx = x->sb;
+  p.e.g1 = g1raw->data; p.e.ldg = g1raw->ld; p.e.sbg = g1raw->sb;
+  p.e.x1 = x1raw->data; p.e.ldx1 = x1raw->ld; p.e.sbx1 = x1raw->sb;
+  p.e.psi = psi->data; p.e.ldq = psi->ld; p.e.sbq = psi->sb;
+  p.e.V = t_vox(x); p.e.B = x->B; p.e.C = x->C; p.e.F = g1raw->C;
+  p.mean_g = bn_g[0]; p.rstd_g = bn_g[1]; p.gam_g = bn_g[2]; p.bet_g = bn_g[3];
+  p.mean_x = bn_x[0]; p.rstd_x = bn_x[1]; p.gam_x = bn_x[2]; p.bet_x = bn_x[3];
+  p.mean_p = bn_p[0]; p.rstd_p = bn_p[1]; p.gam_p = bn_p[2]; p.bet_p = bn_p[3];
+  p.w = w_psi; p.bias = b_psi;
+  return 0;
+}
+
+static bool gate_frozen_tables_ok(const float* const* bn) { return bn && bn[0] && bn[1] && bn[2] && bn[3]; }
+
+extern "C" int coma_gate_frozen_ok(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                                   const coma_tensor* att) {
+  if (!x || !g1raw || !x1raw || !att) return 0;
+  if (!(t_same_grid(x, g1raw) && t_same_grid(x, x1raw) && t_same_grid(x, att) && g1raw->C == x1raw->C && x->C == att->C &&
+        x->dtype == g1raw->dtype && x->dtype == x1raw->dtype && x->dtype == att->dtype)) return 0;
+  const coma_tensor* ts[4] = {x, g1raw, x1raw, att};
+  // the backward runs 4 wide at most (its gradients come in buffers of the same alignment as these)
+  return gate_frozen_vec(x->dtype, ts, 4, x->C, g1raw->C, 4) > 0 ? 1 : 0;
+}
+
+extern "C" int coma_gate_frozen_fwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                                    const float* const* bn_g, const float* const* bn_x, const float* const* bn_p,
+                                    const float* w_psi, const float* b_psi, const coma_tensor* psi, const coma_tensor* att,
+                                    void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COMA_CHECK(x && g1raw && x1raw && psi && att && x->data && g1raw->data && x1raw->data && psi->data && att->data && w_psi &&
+             gate_frozen_tables_ok(bn_g) && gate_frozen_tables_ok(bn_x) && gate_frozen_tables_ok(bn_p), "gate_frozen_fwd: null argument");
+  COMA_CHECK(t_same_grid(x, g1raw) && t_same_grid(x, x1raw) && t_same_grid(x, att) && t_same_grid(x, psi) && psi->C == 1 &&
+             g1raw->C == x1raw->C && x->C == att->C && x->dtype == g1raw->dtype && x->dtype == x1raw->dtype &&
+             x->dtype == att->dtype && psi->dtype == x->dtype, "gate_frozen_fwd: shape/dtype mismatch");
+  const coma_tensor* ts[4] = {x, g1raw, x1raw, att};
+  const int vec = gate_frozen_vec(x->dtype, ts, 4, x->C, g1raw->C, x->dtype == COMA_BF16 ? 8 : 4);
+  COMA_CHECK(vec > 0, "gate_frozen_fwd: C=%d F=%d unsupported (max(C, F) / vector width must be a power of two <= 64)", x->C, g1raw->C);
+  GateFrozenP p{};
+  gate_frozen_common(p, x, g1raw, x1raw, psi, bn_g, bn_x, bn_p, w_psi, b_psi);
+  p.e.att = att->data; p.e.lda = att->ld; p.e.sba = att->sb;
+  p.e.cv = (x->C > g1raw->C ? x->C : g1raw->C) / vec;
+  int cap = 2048 / x->B; if (cap < 1) cap = 1;
+  dim3 grid(gate_blocks(p.e.V, (256 / p.e.cv) * 2, cap), x->B);
+  GATE_DISPATCH(gate_frozen_fwd_k, x->dtype, vec, grid, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int coma_gate_frozen_bwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                                    const coma_tensor* psi, const coma_tensor* datt, const float* const* bn_g,
+                                    const float* const* bn_x, const float* const* bn_p, const float* w_psi, const float* b_psi,
+                                    const coma_tensor* dx, int32_t accumulate_dx, const coma_tensor* dg1raw,
+                                    const coma_tensor* dx1raw, double* rec, float* dgamma_g, float* dbeta_g, float* dgamma_x,
+                                    float* dbeta_x, float* dw_psi, float* db_psi, float* dgamma_psi, float* dbeta_psi,
+                                    void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COMA_CHECK(x && g1raw && x1raw && psi && datt && dx && dg1raw && dx1raw && x->data && g1raw->data && x1raw->data && psi->data &&
+             datt->data && dx->data && dg1raw->data && dx1raw->data && w_psi && rec && gate_frozen_tables_ok(bn_g) &&
+             gate_frozen_tables_ok(bn_x) && gate_frozen_tables_ok(bn_p), "gate_frozen_bwd: null argument");
+  COMA_CHECK(t_same_grid(x, g1raw) && t_same_grid(x, x1raw) && t_same_grid(x, psi) && t_same_grid(x, datt) && t_same_grid(x, dx) &&
+             t_same_grid(x, dg1raw) && t_same_grid(x, dx1raw) && psi->C == 1 && g1raw->C == x1raw->C && g1raw->C == dg1raw->C &&
+             g1raw->C == dx1raw->C && x->C == datt->C && x->C == dx->C, "gate_frozen_bwd: shape mismatch");
+  COMA_CHECK(x->dtype == g1raw->dtype && x->dtype == x1raw->dtype && x->dtype == psi->dtype && x->dtype == datt->dtype &&
+             x->dtype == dx->dtype && x->dtype == dg1raw->dtype && x->dtype == dx1raw->dtype, "gate_frozen_bwd: dtype mismatch");
+  const coma_tensor* ts[7] = {x, g1raw, x1raw, datt, dx, dg1raw, dx1raw};
+  // 4 wide at most: 16 fp64 + 16 fp32 accumulators per lane beside five tensors in flight (8 wide would spill)
+  const int vec = gate_frozen_vec(x->dtype, ts, 7, x->C, g1raw->C, 4);
+  COMA_CHECK(vec > 0, "gate_frozen_bwd: C=%d F=%d unsupported (max(C, F) / vector width must be a power of two <= 64)", x->C, g1raw->C);
+  GateFrozenP p{};
+  gate_frozen_common(p, x, g1raw, x1raw, psi, bn_g, bn_x, bn_p, w_psi, b_psi);
+  p.e.cv = (x->C > g1raw->C ? x->C : g1raw->C) / vec;
+  p.dout = datt->data; p.ldo = datt->ld; p.sbo = datt->sb;
+  p.dx = dx->data; p.lddx = dx->ld; p.sbdx = dx->sb; p.acc = accumulate_dx;
+  p.dg1 = dg1raw->data; p.lddg = dg1raw->ld; p.sbdg = dg1raw->sb;
+  p.dx1 = dx1raw->data; p.lddx1 = dx1raw->ld; p.sbdx1 = dx1raw->sb;
+  p.rec = rec; p.rrs = COMA_NORM_RECORD_DOUBLES(1, g1raw->C + 1, 4);
+  p.dgam_g = dgamma_g; p.dbet_g = dbeta_g; p.dgam_x = dgamma_x; p.dbet_x = dbeta_x; p.dw = dw_psi; p.db = db_psi;
+  p.dgam_p = dgamma_psi; p.dbet_p = dbeta_psi;
+  int cap = 2048 / x->B; if (cap < 1) cap = 1;
+  dim3 grid(gate_blocks(p.e.V, (256 / p.e.cv) * 2, cap), x->B);
+  if (x->dtype == COMA_F32) { if (vec == 4) hipLaunchKernelGGL((gate_frozen_bwd_k<float, 4>), grid, dim3(256), 0, s, p);
+                              else hipLaunchKernelGGL((gate_frozen_bwd_k<float, 1>), grid, dim3(256), 0, s, p); }
+  else { if (vec == 4) hipLaunchKernelGGL((gate_frozen_bwd_k<bf16_t, 4>), grid, dim3(256), 0, s, p);
+         else hipLaunchKernelGGL((gate_frozen_bwd_k<bf16_t, 1>), grid, dim3(256), 0, s, p); }
+  COMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gate_frozen_finalize_k, dim3(1), dim3(256), 0, s, p);
   COMA_LAUNCH_CHECK();
   return 0;
 }

@@ -510,3 +510,152 @@ extern "C" int coma_norm_act_bwd(const coma_tensor* x, const coma_tensor* dy, in
   COMA_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- frozen BatchNorm (train-mode model, running statistics): y = act(gamma (x - m) r + beta) is a per-channel affine map,
+// so its backward needs no statistics of dy: ONE streaming pass over (x, dy) writes dx = dy act'(z) gamma r and, when a
+// parameter gradient is wanted, adds the block's per-channel {sum dz, sum dz xhat, sum dy dact/dslope} to a replica record
+// laid out [3][C] (one tree per kind over 8 KB of LDS).
+template <typename T, int VEC, bool SUMS>
+__global__ __launch_bounds__(256) void norm_act_bwd_frozen_k(RowsP p, const void* dyp, int64_t lddy, int64_t sbdy, void* dxp,
+                                                             int64_t lddx, int64_t sbdx, const float* mean, const float* rstd,
+                                                             const float* gamma, const float* beta, int act,
+                                                             const float* slope, double* bsums, int64_t brs) {
+  const int tid = threadIdx.x, tx = tid % p.cvp, ty = tid / p.cvp;
+  const int64_t r0 = (int64_t)blockIdx.x * p.ch;
+  const int64_t r1 = r0 + p.ch < p.R ? r0 + p.ch : p.R;
+  const float a = slope ? *slope : 0.25f;
+  double s1[VEC], s2[VEC], s3[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { s1[j] = s2[j] = s3[j] = 0.0; }
+  if (tx < p.cv) {
+    const T* xb = reinterpret_cast<const T*>(p.x);
+    const T* dyb = reinterpret_cast<const T*>(dyp);
+    T* ob = reinterpret_cast<T*>(dxp);
+    float mu[VEC], rs[VEC], ga[VEC], be[VEC], gr[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const int c = tx * VEC + j;
+      mu[j] = mean[c]; rs[j] = rstd[c];
+      ga[j] = gamma ? gamma[c] : 1.f; be[j] = gamma ? beta[c] : 0.f;
+      gr[j] = ga[j] * rs[j];
+    }
+    // two rows of both tensors in flight per lane (norm_bwd_partial_k: more costs the occupancy a streaming kernel lives
+    // on); bf16: fp32 partial sums over bursts of 8 rows folded into fp64, fp32: every term straight to fp64
+    constexpr int BURST = sizeof(T) == 2 ? 8 : 2, LD = 2;
+    RowWalk w(p, r0 + ty);
+    while (w.r < r1) {
+      float f1[VEC], f2[VEC], f3[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) { f1[j] = 0.f; f2[j] = 0.f; f3[j] = 0.f; }
+#pragma unroll 1
+      for (int h = 0; h < BURST / LD && w.r < r1; ++h) {
+        float xv[LD][VEC], dv[LD][VEC];
+        bool ok[LD];
+        int64_t ox[LD];
+        // offsets of the last VALID row: a row past the chunk re-reads it and is neither summed nor stored (w.r < r1 holds
+        // for u = 0; the walk itself may step past the tensor and its offsets must never be dereferenced then)
+        int64_t lx = 0, ldd = 0, lo = 0;
+#pragma unroll
+        for (int u = 0; u < LD; ++u) {
+          ok[u] = w.r < r1;
+          if (ok[u]) { lx = w.off(p, 0, p.ld, p.sb); ldd = w.off(p, 0, lddy, sbdy); lo = w.off(p, 0, lddx, sbdx); }
+          ox[u] = lo;
+          vec_io<T, VEC>::load(xb + lx + tx * VEC, xv[u]);
+          vec_io<T, VEC>::load(dyb + ldd + tx * VEC, dv[u]);
+          w.step(p);
+        }
+#pragma unroll
+        for (int u = 0; u < LD; ++u) {
+          float ov[VEC];
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) {
+            const float xh = (xv[u][j] - mu[j]) * rs[j];
+            const float z = xh * ga[j] + be[j];
+            float ds; const float da = act_bwd(act, z, a, &ds);
+            const float dvv = ok[u] ? dv[u][j] : 0.f;
+            const float dz = dvv * da;
+            ov[j] = dz * gr[j];
+            if (SUMS) {
+              if (sizeof(T) == 2) { f1[j] += dz; f2[j] = fmaf(dz, xh, f2[j]); f3[j] = fmaf(dvv, ds, f3[j]); }
+              else { s1[j] += (double)dz; s2[j] += (double)(dz * xh); s3[j] += (double)(dvv * ds); }
+            }
+          }
+          if (ok[u]) vec_io<T, VEC>::store(ob + ox[u] + tx * VEC, ov);
+        }
+      }
+      if (SUMS && sizeof(T) == 2) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) { s1[j] += (double)f1[j]; s2[j] += (double)f2[j]; s3[j] += (double)f3[j]; }
+      }
+    }
+  }
+  if (!SUMS) return;
+  __shared__ double sh[256][VEC];
+#pragma unroll 1
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) sh[tid][j] = k == 0 ? s1[j] : (k == 1 ? s2[j] : s3[j]);
+    __syncthreads();
+    for (int off = p.ry >> 1; off > 0; off >>= 1) {        // tree over the block's rows (see stats_partial_k)
+      if (ty < off) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) sh[tid][j] += sh[tid + off * p.cvp][j];
+      }
+      __syncthreads();
+    }
+    rec_add(bsums, brs, (int64_t)k * p.C, &sh[0][0], p.C);      // row 0 of the tree = a contiguous [C] image of kind k
+    __syncthreads();
+  }
+}
+
+// dbeta / dgamma [C] (=) and dslope [1] (=) out of the [3][C] record of norm_act_bwd_frozen_k
+__global__ __launch_bounds__(256) void norm_frozen_finalize_k(const double* bsums, int64_t brs, int C, float* dgamma, float* dbeta,
+                                                              float* dslope) {
+  __shared__ double ssl[256];
+  double sl = 0.0;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    if (dbeta) dbeta[c] = (float)rec_get(bsums, brs, c);
+    if (dgamma) dgamma[c] = (float)rec_get(bsums, brs, (int64_t)C + c);
+    if (dslope) sl += rec_get(bsums, brs, 2 * (int64_t)C + c);
+  }
+  if (!dslope) return;
+  ssl[threadIdx.x] = sl;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) ssl[threadIdx.x] += ssl[threadIdx.x + o]; __syncthreads(); }
+  if (threadIdx.x == 0) *dslope = (float)ssl[0];
+}
+
+extern "C" int coma_norm_act_bwd_frozen(const coma_tensor* x, const coma_tensor* dy, const float* mean, const float* rstd,
+                                        const float* gamma, const float* beta, int32_t act, const float* slope,
+                                        const coma_tensor* dx, float* dgamma, float* dbeta, float* dslope, double* bsums,
+                                        void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  COMA_CHECK(x && dy && dx && x->data && dy->data && dx->data && mean && rstd, "norm_act_bwd_frozen: null argument");
+  COMA_CHECK(t_same_grid(x, dy) && t_same_grid(x, dx) && x->C == dy->C && x->C == dx->C, "norm_act_bwd_frozen: shape mismatch");
+  COMA_CHECK(x->dtype == dy->dtype && x->dtype == dx->dtype, "norm_act_bwd_frozen: dtype mismatch");
+  COMA_CHECK(!gamma == !beta, "norm_act_bwd_frozen: gamma and beta come together");
+  const bool want = dgamma || dbeta || dslope;
+  COMA_CHECK(!want || bsums, "norm_act_bwd_frozen: parameter gradients need a zeroed record");
+  int vec = (pick_vec(x) == 4 && pick_vec(dy) == 4 && pick_vec(dx) == 4) ? 4 : 1;
+  // 16 bytes per lane for the pure streaming form; with the sums the 8-wide form needs 212 VGPRs (24 fp64 accumulators per
+  // lane: 2 waves per SIMD -- the occupancy norm_bwd_partial_k measured at half the bandwidth) against 116 for the 4-wide one
+  if (!want && pick_vec8(x) == 8 && pick_vec8(dy) == 8 && pick_vec8(dx) == 8) vec = 8;
+  RowsP rp = make_rows(x, COMA_NORM_BATCH, vec);
+  COMA_CHECK(rp.cv <= 256, "norm: C=%d too large", x->C);
+  COMA_CHECK(x->C <= NORM_TAB, "norm: C=%d above the coefficient table size", x->C);
+  const int64_t brs = COMA_NORM_RECORD_DOUBLES(1, rp.C, 3);
+  dim3 pg(rp.nchunks, 1);
+#define L2(T, V, S) hipLaunchKernelGGL((norm_act_bwd_frozen_k<T, V, S>), pg, dim3(256), 0, s, rp, dy->data, dy->ld, dy->sb, \
+                                       dx->data, dx->ld, dx->sb, mean, rstd, gamma, beta, act, slope, bsums, brs)
+#define L(T, V) do { if (want) L2(T, V, true); else L2(T, V, false); } while (0)
+  if (x->dtype == COMA_F32) { if (vec == 4) L(float, 4); else L(float, 1); }
+  else { if (vec == 8) L2(bf16_t, 8, false); else if (vec == 4) L(bf16_t, 4); else L(bf16_t, 1); }
+#undef L
+#undef L2
+  COMA_LAUNCH_CHECK();
+  if (want) {
+    hipLaunchKernelGGL(norm_frozen_finalize_k, dim3(1), dim3(256), 0, s, (const double*)bsums, brs, rp.C, dgamma, dbeta, dslope);
+    COMA_LAUNCH_CHECK();
+  }
+  return 0;
+}

@@ -55,6 +55,9 @@ class Config:
         # take their folded statistics instead of deriving rstd from running_var in every forward
         self.eval_fused = False
         self.eval_stats = None
+        # frozen BatchNorm (model.freeze_batchnorm): in a train-mode model every BatchNorm3d normalises with its running
+        # statistics and never writes them -- the sticky twin of putting the holder nn.BatchNorm3d modules into eval mode
+        self.frozen_bn = False
 
     def begin_forward(self):
         self.nbt_pending = []
@@ -74,7 +77,8 @@ _ACTS = {None: L.ACT_NONE, "relu": L.ACT_RELU, "prelu": L.ACT_PRELU, "leakyrelu"
 
 
 class ADN(nn.Module):
-    """MONAI ADN, ordering "NDA" with p=0 dropout: norm (``N``) then activation (``A``)."""
+    """MONAI ADN, ordering "NDA" with p=0 dropout: norm (``N``) then activation (``A``).  A BatchNorm ``N`` that is in eval
+    mode while this module trains (or ``Config.frozen_bn``) is frozen: running statistics in, none written (bn_frozen)."""
 
     def __init__(self, cfg, channels, act="prelu", norm="instance"):
         super().__init__()
@@ -98,6 +102,34 @@ class ADN(nn.Module):
                         self.training, out)
 
 
+def bn_frozen(cfg, bn):
+    """Is this BatchNorm of a TRAIN-mode owner frozen?  Either the holder module was put into eval mode (the torch idiom:
+    ``for m in model.modules(): if isinstance(m, nn.BatchNorm3d): m.eval()``) or the model's sticky switch is on."""
+    return bn is not None and (cfg.frozen_bn or not bn.training)
+
+
+def frozen_stats(bn, refresh=False):
+    """(mean, rstd) fp32 (1, C) tables of a frozen BatchNorm: m = running_mean, r = rsqrt(running_var + eps).  Made ONCE per
+    BatchNorm and kept on the holder module; refreshed IN PLACE (a captured graph holds their addresses) when the running
+    buffers were written through torch since (load_state_dict bumps their version counters), when a training forward has
+    moved them (_norm_params marks the holder) or on request (model.freeze_batchnorm / the load_state_dict hook)."""
+    rm, rv = bn.running_mean, bn.running_var
+    ent = bn.__dict__.get("_coma_frozen")
+    if ent is None or ent["mean"].device != rm.device or ent["mean"].numel() != rm.numel():
+        C = rm.numel()
+        ent = bn.__dict__["_coma_frozen"] = {"mean": torch.empty((1, C), dtype=torch.float32, device=rm.device),
+                                             "rstd": torch.empty((1, C), dtype=torch.float32, device=rm.device), "key": None}
+    key = (rm.data_ptr(), rv.data_ptr(), rm._version, rv._version, float(bn.eps))
+    if refresh or ent["key"] != key or bn.__dict__.get("_coma_frozen_stale", False):
+        with torch.no_grad():
+            ent["mean"].copy_(rm.reshape(1, -1))
+            torch.add(rv.reshape(1, -1).float(), float(bn.eps), out=ent["rstd"])
+            ent["rstd"].rsqrt_()
+        ent["key"] = key
+        bn.__dict__["_coma_frozen_stale"] = False
+    return ent["mean"], ent["rstd"]
+
+
 def _norm_params(cfg, bn, training):
     gamma = beta = rmean = rvar = None
     momentum, eps = 0.1, 1e-5
@@ -107,6 +139,7 @@ def _norm_params(cfg, bn, training):
         k = cfg.bn_updates_per_forward
         momentum = 1.0 - (1.0 - bn.momentum) ** k     # k identical updates folded into one
         if training:
+            bn.__dict__["_coma_frozen_stale"] = True      # the kernels move the running buffers behind torch's back
             if cfg.nbt_pending is not None:       # the model adds all counters in one multi-tensor launch
                 cfg.nbt_pending.append(bn.num_batches_tracked)
             else:
@@ -116,6 +149,13 @@ def _norm_params(cfg, bn, training):
 
 def norm_act(cfg, x, bn, mode, act, slope, training, out=None, pre=None):
     """`pre`: the statistics record the convolution that wrote `x` produced (ops.ConvLayer with norm=mode)."""
+    if training and mode == L.NORM_BATCH and bn_frozen(cfg, bn):
+        # frozen: the eval form of the forward on the holder's (mean, rstd) tables; no counter, no running update, and a
+        # backward of one pass (ops.NormAct -> coma_norm_act_bwd_frozen)
+        assert pre is None, "a frozen BatchNorm takes no batch statistics: run its convolution with norm=None"
+        gamma, beta, rmean, rvar, momentum, eps = _norm_params(cfg, bn, False)
+        return ops.NormAct.apply(x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, False,
+                                 Out(out) if out is not None else None, None, frozen_stats(bn))
     gamma, beta, rmean, rvar, momentum, eps = _norm_params(cfg, bn, training)
     if cfg.eval_fused and bn is not None and not training and cfg.eval_stats is not None:
         return ops.NormAct.apply(x, gamma, beta, slope, rmean, rvar, mode, act, momentum, eps, training,
@@ -128,8 +168,9 @@ def conv_norm_act(cfg, x, conv_fn, adn, out=None):
     """conv -> ADN with the norm statistics coming out of the conv pass (MONAI Convolution / CondConvolution)."""
     bn = adn.N if adn.mode == L.NORM_BATCH else None
     slope = adn.A.weight if adn.act_name in ("prelu", "prelu_relu") else None
-    if adn.mode == L.NORM_BATCH and not adn.training:     # eval: running statistics, plain conv
-        return norm_act(cfg, conv_fn(None), bn, adn.mode, _ACTS[adn.act_name], slope, False, out)
+    if adn.mode == L.NORM_BATCH and (not adn.training or bn_frozen(cfg, bn)):
+        # eval or frozen: running statistics, plain conv (no statistics epilogue; frozen: its bias gradient is real)
+        return norm_act(cfg, conv_fn(None), bn, adn.mode, _ACTS[adn.act_name], slope, adn.training, out)
     y, sums = conv_fn(adn.mode)
     return norm_act(cfg, y, bn, adn.mode, _ACTS[adn.act_name], slope, adn.training, out, pre=sums)
 
@@ -137,9 +178,10 @@ def conv_norm_act(cfg, x, conv_fn, adn, out=None):
 def conv_then_bn(cfg, x, cv, bn, act, training, out=None):
     """``nn.Sequential(Convolution(conv_only=True), BatchNorm3d[, act])`` (the attention gate's W_g / W_x / psi,
     attn_unet_data_parallel.py:104-137 via MONAI AttentionBlock): the batch statistics come out of the convolution pass
-    and the convolution's bias -- removed again by the BatchNorm -- gets its exact zero gradient."""
-    if not training:
-        return norm_act(cfg, cv(x), bn, L.NORM_BATCH, act, None, False, out)
+    and the convolution's bias -- removed again by the BatchNorm -- gets its exact zero gradient.  A frozen BatchNorm
+    (bn_frozen) removes nothing: plain convolution, real bias gradient."""
+    if not training or bn_frozen(cfg, bn):
+        return norm_act(cfg, cv(x), bn, L.NORM_BATCH, act, None, training, out)
     y, sums = conv_plain(cfg, x, cv.conv, cv.k, cv.s, cv.transposed, None, L.NORM_BATCH)
     return norm_act(cfg, y, bn, L.NORM_BATCH, act, None, True, out, pre=sums)
 

@@ -1066,22 +1066,38 @@ class NormAct(Function):
                         name="norm_act_fwd_k<%s, %d>" % ("__bf16" if x.dtype == torch.bfloat16 else "float", 8 if (x.dtype == torch.bfloat16 and C % 8 == 0) else (4 if C % 4 == 0 else 1)))
         ctx.save_for_backward(x, sums, gamma, beta, slope)
         ctx.meta = (mode, act, use_batch_stats, eps)
+        # running statistics: the backward (frozen BatchNorm) reads the same tables -- persistent ones are refreshed in
+        # place between steps, so they are kept beside the saved tensors, not among them
+        ctx.frozen_mr = (mean, rstd) if not use_batch_stats else None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, sums, gamma, beta, slope = ctx.saved_tensors
         mode, act, use_batch_stats, eps = ctx.meta
-        if not use_batch_stats:
-            raise RuntimeError("backward through eval-mode BatchNorm is not part of the training path")
         dev = x.device
         B, C = x.shape[0], x.shape[4]
         G = B if mode == L.NORM_INSTANCE else 1
         dx = _new(x.shape, x.dtype, dev)
         sinks = GradSink.slots(ctx.params)      # one kernel chain writes all three: one flush, then three marks
-        dgamma = sinks[0] if sinks[0] is not None else (_f32(C, dev) if gamma is not None else None)
-        dbeta = sinks[1] if sinks[1] is not None else (_f32(C, dev) if beta is not None else None)
-        dslope = sinks[2] if sinks[2] is not None else (_f32(1, dev) if slope is not None else None)
+        need = ctx.needs_input_grad[1:4] if not use_batch_stats else (True, True, True)
+        dgamma = sinks[0] if sinks[0] is not None else (_f32(C, dev) if gamma is not None and need[0] else None)
+        dbeta = sinks[1] if sinks[1] is not None else (_f32(C, dev) if beta is not None and need[1] else None)
+        dslope = sinks[2] if sinks[2] is not None else (_f32(1, dev) if slope is not None and need[2] else None)
+        if not use_batch_stats:
+            # frozen BatchNorm: a per-channel affine map -- one pass over (x, dy), no statistics of dy (csrc/norm.hip,
+            # norm_act_bwd_frozen_k); a pure streaming pass without a record when no parameter gradient is wanted
+            mean, rstd = ctx.frozen_mr
+            want = dgamma is not None or dbeta is not None or dslope is not None
+            bsums = stat_record(1, C, 3, dev) if want else None
+            tb = float(x.numel() * x.element_size())      # algorithmic bytes: x and dy read once, dx written once
+            KernelTimer.run("norm_bwd", "hbm", (0.0, 3.0 * tb),
+                            lambda: check(lib.coma_norm_act_bwd_frozen(ct(x), ct(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), act,
+                                                                       ptr(slope), ct(dx), ptr(dgamma), ptr(dbeta), ptr(dslope),
+                                                                       ptr(bsums), L.stream()), "coma_norm_act_bwd_frozen"),
+                            name="norm_act_bwd_frozen_k<%s>" % ("__bf16" if x.dtype == torch.bfloat16 else "float"))
+            return (dx, None if sinks[0] is not None else dgamma, None if sinks[1] is not None else dbeta,
+                    None if sinks[2] is not None else dslope, None, None, None, None, None, None, None, None, None, None)
         bsums = stat_record(G, C, 3, dev)
         tb = float(x.numel() * x.element_size())          # algorithmic bytes: (x, dy) read twice + dx written once
         KernelTimer.run("norm_bwd", "hbm", (0.0, 5.0 * tb),
@@ -1208,6 +1224,87 @@ class GateFused(Function):
         w_shape = ctx.params[4].shape
         return (None if shared else dx, dg1, dx1, None, None, ret(0, dgg), ret(1, dbg), ret(2, dgx), ret(3, dbx),
                 ret(4, dw.view(w_shape)), db_psi, ret(5, dgp), ret(6, dbp), None, None, None, None)
+
+
+def gate_frozen_ok(x, g1raw, x1raw, att):
+    """Do the fused frozen-gate kernels take these tensors (csrc/gate.hip: coma_gate_frozen_ok)?"""
+    return bool(lib.coma_gate_frozen_ok(ct(x), ct(g1raw), ct(x1raw), ct(att)))
+
+
+def _bn_table(mr, gamma, beta):
+    """{mean, rstd, gamma, beta} device pointers of one frozen BatchNorm, as the frozen-gate entry points take them."""
+    import ctypes
+    return (ctypes.c_void_p * 4)(ptr(mr[0]), ptr(mr[1]), ptr(gamma), ptr(beta))
+
+
+class GateFrozen(Function):
+    """The attention gate behind its W_g / W_x convolutions with all three BatchNorms FROZEN (running statistics; the
+    convolutions run plain, with their biases): one launch forward, one pass + a one-block finalise backward
+    (csrc/gate.hip: gate_frozen_fwd_k / gate_frozen_bwd_k).  Only psi is saved: the backward recomputes t, s and psi_raw
+    from g1raw / x1raw, which it reads anyway.  `stats`: ((mean, rstd) of BN_g, of BN_x, of BN_psi) -- layers.frozen_stats.
+    Returns (att, psi); psi is for inspection only (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x, g1raw, x1raw, gam_g, bet_g, gam_x, bet_x, w_psi, b_psi, gam_p, bet_p, stats, out):
+        ctx.set_materialize_grads(False)
+        dev, dt = x.device, x.dtype
+        B, D, H, W, C = x.shape
+        F_ = g1raw.shape[4]
+        wv = w_psi.reshape(-1)
+        assert wv.is_contiguous() and wv.dtype == torch.float32 and wv.numel() == F_
+        psi = _new((B, D, H, W, 1), dt, dev)
+        att = out.t if out is not None else _new(x.shape, dt, dev)
+        tabs = (_bn_table(stats[0], gam_g, bet_g), _bn_table(stats[1], gam_x, bet_x), _bn_table(stats[2], gam_p, bet_p))
+        tb = float(x.numel() * x.element_size())
+        fb = float(g1raw.numel() * g1raw.element_size())
+        KernelTimer.run("gate_frozen_fwd", "hbm", (0.0, 2.0 * tb + 2.0 * fb),
+                        lambda: check(lib.coma_gate_frozen_fwd(ct(x), ct(g1raw), ct(x1raw), tabs[0], tabs[1], tabs[2], ptr(wv), ptr(b_psi),
+                                                               ct(psi), ct(att), L.stream()), "coma_gate_frozen_fwd"),
+                        tag=tuple(x.shape), name="gate_frozen_fwd_k<%s>" % ("__bf16" if dt == torch.bfloat16 else "float"))
+        ctx.save_for_backward(x, g1raw, x1raw, psi, gam_g, bet_g, gam_x, bet_x, gam_p, bet_p, wv)
+        ctx.params = (gam_g, bet_g, gam_x, bet_x, w_psi, b_psi, gam_p, bet_p)
+        ctx.stats = stats          # (persistent tables, refreshed in place between steps: kept beside the saved tensors)
+        ctx.fork = getattr(x, "_coma_fork", None)
+        ctx.mark_non_differentiable(psi)
+        return att, psi
+
+    @staticmethod
+    def backward(ctx, datt, _dpsi):
+        n_in = 13
+        if datt is None:
+            return (None,) * n_in
+        x, g1raw, x1raw, psi, gam_g, bet_g, gam_x, bet_x, gam_p, bet_p, wv = ctx.saved_tensors
+        b_psi = ctx.params[5]
+        dev, dt = x.device, x.dtype
+        F_ = g1raw.shape[4]
+        fork = ctx.fork
+        if fork is not None and fork.buf is not None:
+            dx, acc, shared = fork.buf, 1, True
+        else:
+            dx, acc, shared = _new(x.shape, dt, dev), 0, fork is not None
+            if shared:
+                fork.buf = dx
+        sinks = GradSink.slots(ctx.params)          # one kernel chain writes all eight: one flush, then the marks
+        fresh = lambda i, n: sinks[i] if sinks[i] is not None else (_f32(n, dev) if ctx.params[i] is not None else None)
+        dgg, dbg, dgx, dbx, dw = fresh(0, F_), fresh(1, F_), fresh(2, F_), fresh(3, F_), fresh(4, F_)
+        db, dgp, dbp = fresh(5, 1), fresh(6, 1), fresh(7, 1)
+        rec = stat_record(1, F_ + 1, 4, dev)
+        dg1 = _new(g1raw.shape, dt, dev)
+        dx1 = _new(x1raw.shape, dt, dev)
+        stats = ctx.stats
+        tabs = (_bn_table(stats[0], gam_g, bet_g), _bn_table(stats[1], gam_x, bet_x), _bn_table(stats[2], gam_p, bet_p))
+        tb = float(x.numel() * x.element_size())
+        fb = float(g1raw.numel() * g1raw.element_size())
+        KernelTimer.run("gate_frozen_bwd", "hbm", (0.0, (3.0 + acc) * tb + 4.0 * fb),
+                        lambda: check(lib.coma_gate_frozen_bwd(ct(x), ct(g1raw), ct(x1raw), ct(psi), ct(datt), tabs[0], tabs[1], tabs[2],
+                                                               ptr(wv), ptr(b_psi), ct(dx), acc, ct(dg1), ct(dx1), ptr(rec), ptr(dgg),
+                                                               ptr(dbg), ptr(dgx), ptr(dbx), ptr(dw), ptr(db), ptr(dgp), ptr(dbp),
+                                                               L.stream()), "coma_gate_frozen_bwd"),
+                        tag=tuple(x.shape), name="gate_frozen_bwd_k<%s>" % ("__bf16" if dt == torch.bfloat16 else "float"))
+        ret = lambda i, t: None if sinks[i] is not None else t
+        w_shape = ctx.params[4].shape
+        return (None if shared else dx, dg1, dx1, ret(0, dgg), ret(1, dbg), ret(2, dgx), ret(3, dbx),
+                ret(4, dw.view(w_shape)), ret(5, db), ret(6, dgp), ret(7, dbp), None, None)
 
 
 def gate_eval_mfma_ok(g, x, f_int):

@@ -104,8 +104,13 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        optimizer keeps its own settings): one update per ``grad_acc_batch`` batches with the mean of their gradients,
        clipped to that global norm.  A window still open at the end of an epoch is applied there (``optimizer.flush()``,
        the reference's "ensure BP on the remaining accumulated batches", :918-920), before the scheduler step and the
-       checkpoint.  Not available together with ``reducer`` (ValueError)."""
+       checkpoint.  Not available together with ``reducer`` (ValueError).
+     * ``freeze_bn``: when given, ``model.freeze_batchnorm(freeze_bn)`` before the first epoch (else the model stays as
+       the caller set it) -- every BatchNorm3d normalises with its running statistics and leaves them alone (fine-tuning
+       a resumed checkpoint); the switch survives the ``model.train(True)`` of every epoch."""
     import torch.distributed as dist
+    if "freeze_bn" in kwargs:
+        model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
     cwd = os.getcwd()
     fold = kwargs.get("fold_id")
     base = f"{cwd}/training_folds/adni_a4_first_scan_combined_folds/tau_prediction_lookups"

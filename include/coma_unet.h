@@ -258,6 +258,20 @@ int coma_norm_act_fwd(const coma_tensor* x, int32_t mode, const double* sums, fl
 int coma_norm_act_bwd(const coma_tensor* x, const coma_tensor* dy, int32_t mode, const double* sums, float eps,
                       const float* gamma, const float* beta, int32_t act, const float* slope,
                       const coma_tensor* dx, float* dgamma, float* dbeta, float* dslope, double* bsums, void* stream);
+/* Backward through a FROZEN BatchNorm3d (+ activation): a train-mode model that normalises with the running statistics.
+ * With m = running_mean and r = rsqrt(running_var + eps) handed in as the fp32 tables mean / rstd [C] (the form
+ * coma_norm_act_fwd takes when sums == NULL; that call is the forward):
+ *     xhat = (x - m) r        z = gamma xhat + beta        y = act(z)
+ *     dz = dy act'(z)         dx (=) dz gamma r
+ *     dgamma (=) sum dz xhat  dbeta (=) sum dz             dslope (=) sum dy dact/dslope
+ * No statistics of dy are needed: one streaming pass over (x, dy) (16 bytes per lane on bf16 without, 8 with the
+ * sums), plus one one-block finalise launch when any of dgamma / dbeta / dslope is wanted (each may be NULL).  bsums: ZEROED fp64 record [COMA_STAT_REPLICAS][3][C], replica
+ * stride COMA_NORM_RECORD_DOUBLES(1, C, 3); may be NULL when no parameter gradient is wanted (the pass then touches no
+ * record).  gamma / beta may both be NULL.  The running statistics are not written.                                  */
+int coma_norm_act_bwd_frozen(const coma_tensor* x, const coma_tensor* dy, const float* mean, const float* rstd,
+                             const float* gamma, const float* beta, int32_t act, const float* slope,
+                             const coma_tensor* dx, float* dgamma, float* dbeta, float* dslope, double* bsums,
+                             void* stream);
 
 /* ---- attention gate pieces (MONAI AttentionBlock, attn_unet_data_parallel.py:139-150) ---- */
 /* out = relu(a + b);  da (=) db (=) dout * [out > 0] */
@@ -308,6 +322,37 @@ int coma_gate_mid_bwd(const coma_tensor* dz, const coma_tensor* psi_raw, const c
 int coma_gate_eval_fwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw, const float* scale_g,
                        const float* scale_x, const float* shift, const float* w_psi, const float* psi_ab,
                        const coma_tensor* psi, const coma_tensor* att, void* stream);
+/* ---- the attention gate with every BatchNorm FROZEN (a train-mode model on running statistics), behind the W_g / W_x
+ * convolutions, which run plain (with their biases, no statistics epilogue).  Per BatchNorm a table of four device
+ * pointers bn[4] = {mean, rstd, gamma, beta} (fp32; F entries for g and x, one for psi) with m = running_mean and
+ * r = rsqrt(running_var + eps) made once by the caller -- nothing is re-folded on the device between steps:
+ *     t = gamma_g ghat + beta_g + gamma_x x1hat + beta_x     s = relu(t)     pr = w_psi . s + b_psi
+ *     zhat = (pr - m_p) r_p     psi = sigmoid(gamma_p zhat + beta_p)         att = x psi
+ * backward:
+ *     dx (= or +=) datt psi     dpsi = sum_c datt x     dzp = dpsi psi (1 - psi)
+ *     dgamma_p = sum dzp zhat   dbeta_p = sum dzp       dpr = dzp gamma_p r_p     db_psi = sum dpr
+ *     dw_f = sum dpr s_f        d_f = dpr w_f [t_f > 0]
+ *     dg1raw_f = d_f gamma_g,f r_g,f        dx1raw_f = d_f gamma_x,f r_x,f
+ *     dgamma_g,f = sum d_f ghat_f           dbeta_g,f = sum d_f      (and the same for x)
+ * Forward: one launch; writes psi ([B][V][1], read again by the backward) and att (may be a channel slice).  s is not
+ * saved: the backward reads g1raw / x1raw anyway (ghat, x1hat) and recomputes t, s and pr in registers.
+ * Backward: one pass over the voxels + a one-block finalise launch.  dx may accumulate (accumulate_dx) into a shared
+ * gradient buffer; datt may be a channel slice.  rec: ZEROED fp64 record
+ * [COMA_STAT_REPLICAS][COMA_NORM_RECORD_DOUBLES(1, F + 1, 4)].  Parameter gradients (=); any may be NULL; b_psi may be NULL.
+ * Envelope (coma_gate_frozen_ok): one dtype, C and F multiples of the vector width (4, or 1 for unaligned tensors) and
+ * max(C, F) / width a power of two <= 64, F <= 512 -- what the training gate kernels take.                          */
+int coma_gate_frozen_ok(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw, const coma_tensor* att);
+int coma_gate_frozen_fwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                         const float* const* bn_g, const float* const* bn_x, const float* const* bn_psi,
+                         const float* w_psi, const float* b_psi, const coma_tensor* psi, const coma_tensor* att,
+                         void* stream);
+int coma_gate_frozen_bwd(const coma_tensor* x, const coma_tensor* g1raw, const coma_tensor* x1raw,
+                         const coma_tensor* psi, const coma_tensor* datt, const float* const* bn_g,
+                         const float* const* bn_x, const float* const* bn_psi, const float* w_psi, const float* b_psi,
+                         const coma_tensor* dx, int32_t accumulate_dx, const coma_tensor* dg1raw,
+                         const coma_tensor* dx1raw, double* rec, float* dgamma_g, float* dbeta_g, float* dgamma_x,
+                         float* dbeta_x, float* dw_psi, float* db_psi, float* dgamma_psi, float* dbeta_psi,
+                         void* stream);
 /* The whole gate INCLUDING both 1x1x1 convolutions in one launch (bf16 MFMA, no intermediate ever in memory):
  * wg_folded / wx_folded are bf16 [32][C] = diag(scale_g) W_g, diag(scale_x) W_x with ZERO rows beyond F, and shift / w_psi
  * here have 32 entries, zero beyond F (shift carries the biases): the padded rows contribute exactly nothing.
