@@ -7,6 +7,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is absent)
 from .attn_unet_data_parallel import (ContrastiveAttentionUNET_DP, ObservableAttentionUnet, AttentionLayer,
                                       ObservableAttentionBlock, UpBlock, ProjectionHead, StackedFusionConvLayers)
 from .inference import Predictor, fold_gate
+from .optim import FusedAdamW
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, build_reference_criterion
 
 DEFAULT_MODEL_PARAMS = (3, 1, 1, [32, 64, 128, 256, 512], [2] * 5)   # validation.py:727

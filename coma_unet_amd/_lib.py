@@ -121,6 +121,9 @@ SIGNATURES = {
     "coma_grad_accum": (_i32, [_vp, _vp, _i64, _vp, _vp, C.POINTER(_i32), _vp]),
     "coma_adamw_ex": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp, _f32,
                              _vp, _vp]),
+    "coma_adamw_ema": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp, _f32,
+                              _vp, _vp, _f32, _i32, _vp]),
+    "coma_swap_f32": (_i32, [_vp, _vp, _i64, _vp]),
 }
 
 

@@ -2,6 +2,10 @@
 
     {'epoch', 'model_state_dict', 'optimizer_state_dict', 'loss', 'scheduler_state_dict'}
 
+plus ``'ema_state_dict'`` when the optimizer keeps a weight average (``FusedAdamW(ema_decay=...)``): a second
+``model.state_dict()``-shaped dict with the averaged weights (``FusedAdamW.ema_state_dict``).  The five keys above are
+unchanged, so the reference's loader reads such a file as before and ignores the sixth.
+
 ``model_state_dict`` carries the reference's key names (this build's module tree mirrors the MONAI / CondConv one),
 ``optimizer_state_dict`` is ``torch.optim.AdamW``-shaped (``FusedAdamW.state_dict``), so a file written here loads into
 the reference stack and vice versa.  Files are read with ``weights_only=True`` (nothing in them needs unpickling).
@@ -18,6 +22,8 @@ def checkpoint_dict(epoch, model, optimizer, loss, scheduler=None):
             "loss": loss.detach().cpu() if torch.is_tensor(loss) else loss}
     if scheduler is not None:
         ckpt["scheduler_state_dict"] = scheduler.state_dict()
+    if getattr(optimizer, "averaging", False):
+        ckpt["ema_state_dict"] = optimizer.ema_state_dict(model)
     return ckpt
 
 
@@ -40,11 +46,16 @@ def save_checkpoint(save_path, epoch, model, optimizer, loss, scheduler=None, ch
 
 
 def load_checkpoint(path, model, optimizer=None, scheduler=None, map_location="cpu"):
-    """validation.py:221-281: returns the epoch to resume at (saved epoch + 1)."""
+    """validation.py:221-281: returns the epoch to resume at (saved epoch + 1).  The weight average is restored when both
+    the file and the optimizer have one; a file without it leaves the average to start from the loaded parameters."""
     ckpt = torch.load(path, map_location=map_location, weights_only=True)
     model.load_state_dict(ckpt["model_state_dict"])
     if optimizer is not None:
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        if getattr(optimizer, "averaging", False):
+            optimizer.reset_ema()
+            if "ema_state_dict" in ckpt:
+                optimizer.load_ema_state_dict(model, ckpt["ema_state_dict"])
     if scheduler is not None and "scheduler_state_dict" in ckpt:
         scheduler.load_state_dict(ckpt["scheduler_state_dict"])
     return int(ckpt["epoch"]) + 1

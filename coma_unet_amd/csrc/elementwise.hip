@@ -650,3 +650,104 @@ extern "C" int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64
   COMA_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- weight EMA inside the AdamW sweep (optim.FusedAdamW(ema_decay, ema_warmup)) ----
+// adamw_ex_k's update of p, m, v, statement for statement (with no counter and no partials s is 1.0f and the three are
+// bitwise adamw_k's), then e += (1 - d_t)(p' - e) on the parameter just computed, while it is still in registers: 8 more
+// bytes per element instead of a 12-byte pass of its own.  d_t is formed here, in fp32, from the same device step count
+// the bias corrections read, so a replayed graph moves through the warm-up.
+__global__ __launch_bounds__(256) void adamw_ema_k(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr,
+                                                   float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                   int step, const int32_t* step_dev, const int32_t* count_dev,
+                                                   const double* partials, int n_partials, const double* extra_sumsq,
+                                                   float max_norm, float* norm_out, float ema_decay, int ema_warmup, int vec4) {
+  __shared__ double sh[4];
+  float st = (float)step;
+  if (step_dev) {
+    st = (float)*step_dev;
+    bc1 = 1.f - powf(b1, st);
+    bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  }
+  const double count = count_dev ? (double)*count_dev : 1.0;
+  double c = 1.0;
+  if (partials) {                                   // (kernel argument: the whole block takes the branch)
+    double t = 0.0;
+    for (int k = threadIdx.x; k < n_partials; k += 256) t += partials[k];
+    t = ew_block_sum(t, sh);
+    if (extra_sumsq) t += *extra_sumsq;
+    const double norm = sqrt(t) / count;
+    const double x = (double)max_norm / (norm + 1e-6);
+    c = x > 1.0 ? 1.0 : x;
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
+  }
+  const float s = (float)(c / count);
+  const float d = ema_warmup ? fminf(ema_decay, (1.f + st) / (10.f + st)) : ema_decay;
+  const float w = 1.f - d;
+  auto upd = [&](float& pi, float gr, float& mi, float& vi, float& ei) {
+    const float gi = gr * s;
+    pi *= (1.f - lr * wd);
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    ei = fmaf(w, pi - ei, ei);
+  };
+  const int64_t n4 = vec4 ? n >> 2 : 0;        // 16 bytes per lane and stream where the five buffers are 16-byte aligned
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    float4 ev = reinterpret_cast<float4*>(e)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    upd(pv.x, gv.x, mv.x, vv.x, ev.x); upd(pv.y, gv.y, mv.y, vv.y, ev.y);
+    upd(pv.z, gv.z, mv.z, vv.z, ev.z); upd(pv.w, gv.w, mv.w, vv.w, ev.w);
+    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(e)[i] = ev;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float pi = p[i], mi = m[i], vi = v[i], ei = e[i];
+    upd(pi, g[i], mi, vi, ei);
+    p[i] = pi; m[i] = mi; v[i] = vi; e[i] = ei;
+  }
+}
+extern "C" int coma_adamw_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                              float eps, float weight_decay, int32_t step, const int32_t* step_dev, const int32_t* count_dev,
+                              const double* partials, int32_t n_partials, const double* extra_sumsq, float max_norm,
+                              float* norm_out, float* ema, float ema_decay, int32_t ema_warmup, void* stream) {
+  COMA_CHECK(n >= 0 && (step >= 1 || step_dev), "adamw_ema: bad argument");
+  COMA_CHECK(!partials || (n_partials >= 0 && n_partials <= ACC_BLOCKS && max_norm >= 0.f),
+             "adamw_ema: %d partials (at most %d), max_norm %g", n_partials, (int)ACC_BLOCKS, (double)max_norm);
+  COMA_CHECK(ema_decay > 0.f && ema_decay < 1.f, "adamw_ema: ema_decay %g is not inside (0, 1)", (double)ema_decay);
+  if (n == 0) return 0;
+  COMA_CHECK(p && g && m && v && ema, "adamw_ema: null argument");
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2 = 1.f - powf(beta2, (float)step);
+  const int vec4 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)ema)) & 15) == 0;
+  hipLaunchKernelGGL(adamw_ema_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr,
+                     beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), (int)step, step_dev, count_dev, partials, (int)n_partials,
+                     extra_sumsq, max_norm, norm_out, ema_decay, (int)ema_warmup, vec4);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// a <-> b by content: the parameters and their average change places while every address a captured graph or a parameter
+// view holds stays what it was
+__global__ __launch_bounds__(256) void swap_f32_k(float* a, float* b, int64_t n, int vec4) {
+  const int64_t n4 = vec4 ? n >> 2 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 av = reinterpret_cast<float4*>(a)[i], bv = reinterpret_cast<float4*>(b)[i];
+    reinterpret_cast<float4*>(a)[i] = bv; reinterpret_cast<float4*>(b)[i] = av;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float ai = a[i], bi = b[i];
+    a[i] = bi; b[i] = ai;
+  }
+}
+extern "C" int coma_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  COMA_CHECK(n >= 0, "swap_f32: n = %lld", (long long)n);
+  if (n == 0) return 0;
+  COMA_CHECK(a && b, "swap_f32: null argument");
+  COMA_CHECK(a != b && (a + n <= b || b + n <= a), "swap_f32: the two buffers are the same or overlap");
+  const int vec4 = ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0;
+  hipLaunchKernelGGL(swap_f32_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, a, b, n, vec4);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}

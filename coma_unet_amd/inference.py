@@ -101,7 +101,13 @@ class Predictor:
     reference's list of dicts).  The returned tensor is the predictor's own output buffer: the next call rewrites it.
     The model is left as it was found: its mode flags are restored after every forward, and parameters, running
     statistics and num_batches_tracked are never written (eval mode, no_grad).  graph=False runs the same fast path
-    eagerly."""
+    eagerly.
+
+    Predicting from the weight average of ``FusedAdamW(ema_decay=...)``: either load it into a model of its own
+    (``model.load_state_dict(ckpt["ema_state_dict"])``, then build the Predictor on that model), or build or ``refresh()``
+    the Predictor inside ``with optimizer.ema_weights():`` -- the swap is by content, so the captured graph's addresses
+    stay valid; the folds are copies of the parameters' values, so ``refresh()`` once more after the block to predict
+    from the iterate again."""
 
     def __init__(self, model, batch, graph=True, warmup=2):
         if getattr(model, "embeddings_out", False):

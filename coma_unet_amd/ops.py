@@ -1524,3 +1524,20 @@ def adamw_ex_(p, g, m, v, lr, beta1, beta2, eps, wd, step, step_dev=None, count_
     check(lib.coma_adamw_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step, ptr(step_dev),
                             ptr(count_dev), ptr(partials), n_partials, ptr(extra_sumsq), max_norm, ptr(norm_out), L.stream()),
           "coma_adamw_ex")
+
+
+def adamw_ema_(p, g, m, v, ema, ema_decay, ema_warmup, lr, beta1, beta2, eps, wd, step, step_dev=None, count_dev=None,
+               partials=None, n_partials=0, extra_sumsq=None, max_norm=0.0, norm_out=None):
+    """adamw_ex_ (adamw_ with the defaults) and, in the same sweep, ema += (1 - d_t) (p' - ema) on the updated parameter:
+    d_t = ema_decay, or min(ema_decay, (1 + t) / (10 + t)) with ema_warmup (t: the update count, from `step_dev` when given)."""
+    assert p.is_contiguous() and g.is_contiguous() and p.dtype == torch.float32 and g.dtype == torch.float32
+    assert ema.is_contiguous() and ema.dtype == torch.float32 and ema.numel() == p.numel()
+    check(lib.coma_adamw_ema(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step, ptr(step_dev),
+                             ptr(count_dev), ptr(partials), n_partials, ptr(extra_sumsq), max_norm, ptr(norm_out), ptr(ema),
+                             ema_decay, int(bool(ema_warmup)), L.stream()), "coma_adamw_ema")
+
+
+def swap_f32_(a, b):
+    """Exchange the contents of two disjoint contiguous fp32 tensors in place (one launch)."""
+    assert a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype == torch.float32 and a.numel() == b.numel()
+    check(lib.coma_swap_f32(ptr(a), ptr(b), a.numel(), L.stream()), "coma_swap_f32")

@@ -12,6 +12,12 @@ exactly as torch does (no decay, no moment update, no step count): the reference
 step's own kernels (``ops.grad_accum_`` / ``ops.adamw_ex_``), replay-safe.  The gradient applied is the MEAN over the
 window's micro-batches (the ``(loss / K).backward()`` idiom; the reference's commented-out ``grad_acc_batch`` lines,
 attn_unet_data_parallel.py:887-890, do not divide -- the mean keeps ``lr`` comparable across K).
+
+``ema_decay=d`` / ``ema_warmup``: an exponential moving average of the weights, moved by the update's own kernel
+(``ops.adamw_ema_``: the parameter is in registers there already) into ``flat_ema``, a buffer with ``flat_p``'s layout;
+``swap_ema()`` / ``ema_weights()`` exchange parameters and average by content (``ops.swap_f32_``), so that every view and every
+captured graph keeps its address; ``ema_state_dict`` / ``load_ema_state_dict`` serialise it.  With the option off nothing of it
+exists.
 """
 from __future__ import annotations
 
@@ -32,6 +38,19 @@ def _check_window_opts(grad_acc_batch, max_grad_norm):
         raise ValueError(f"max_grad_norm must be None or >= 0, got {max_grad_norm!r}")
 
 
+NO_EMA_SHARDED = ("ema_decay is not supported under a sharded gradient exchange (StreamedGradExchange(sharded=True)): each rank "
+                  "updates only its own slices of the parameters there, and the averages of the other slices are not gathered")
+EMA_IN = "the averaged weights are swapped in (swap_ema() / ema_weights()): swap them out before {}"
+
+
+def _check_ema_opts(ema_decay, ema_warmup):
+    if ema_decay is not None:
+        if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be None or lie strictly inside (0, 1), got {ema_decay!r}")
+    if not isinstance(ema_warmup, (bool, int)) or ema_warmup not in (0, 1):
+        raise ValueError(f"ema_warmup must be a bool, got {ema_warmup!r}")
+
+
 def check_no_exchange(optimizer, reducer):
     """ValueError when a gradient exchange meets an optimizer that accumulates or clips."""
     if reducer is not None and getattr(optimizer, "windowed", False):
@@ -40,14 +59,21 @@ def check_no_exchange(optimizer, reducer):
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, dynamic=(), write_through=False,
-                 pad_to=1, grad_acc_batch=1, max_grad_norm=None):
+                 pad_to=1, grad_acc_batch=1, max_grad_norm=None, ema_decay=None, ema_warmup=False):
         """grad_acc_batch=K > 1: ``step()`` means "this micro-batch's backward is done" -- it adds the flat gradient to a flat
         fp32 accumulator and the K-th call (or ``flush()``) applies ONE update with the MEAN of the window's gradients.
         max_grad_norm: clip that mean gradient to this global 2-norm first (``torch.nn.utils.clip_grad_norm_``; the
-        unclipped norm is left in ``last_grad_norm``, a device float).  Both live in ``param_groups[0]``."""
+        unclipped norm is left in ``last_grad_norm``, a device float).  Both live in ``param_groups[0]``.
+        ema_decay=d: every applied update also moves an exponential moving average of the weights, e += (1 - d_t)(p - e),
+        inside the update's own kernel (``ops.adamw_ema_``); d_t = d, or min(d, (1 + t) / (10 + t)) with ema_warmup (t: the
+        update count).  The average starts at the parameters' values when the option is switched on.  ``swap_ema()`` /
+        ``ema_weights()`` put it under the model, ``ema_state_dict`` / ``load_ema_state_dict`` serialise it.  Both options
+        live in ``param_groups[0]`` too."""
         _check_window_opts(grad_acc_batch, max_grad_norm)
+        _check_ema_opts(ema_decay, ema_warmup)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_acc_batch=int(grad_acc_batch),
-                        max_grad_norm=None if max_grad_norm is None else float(max_grad_norm))
+                        max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
+                        ema_decay=None if ema_decay is None else float(ema_decay), ema_warmup=bool(ema_warmup))
         super().__init__(params, defaults)
         assert len(self.param_groups) == 1, "one parameter group (the reference uses one)"
         self._dynamic = {id(p) for p in dynamic}   # may or may not get a gradient, step to step
@@ -79,6 +105,11 @@ class FusedAdamW(torch.optim.Optimizer):
         self._loose_acc = {}           # parameter outside the flat buffer -> its fp32 accumulator (all zeros between windows)
         self._loose_live = set()       # ids of those that received a gradient in the open window
         self.last_grad_norm = None
+        # weight EMA (ema_decay; allocated by _ensure_ema, none of it exists on the default path)
+        self.flat_ema = None           # the average of flat_p, same layout
+        self._loose_ema = {}           # parameter outside the flat buffer -> its average (flat fp32), from its first step on
+        self._ema_parked = {}          # parameter -> average loaded before the flat layout existed (load_ema_state_dict)
+        self._ema_in = False           # swap_ema(): the parameters hold the average, flat_ema / _loose_ema the iterate
 
     # -- layout -------------------------------------------------------------------------
     def _build(self):
@@ -115,6 +146,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self.flat_v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
                 self._flat_step = max(self._flat_step, int(st["step"]))
         self._step_dev = torch.full((1,), self._flat_step, dtype=torch.int32, device=dev)
+        self._ensure_ema()
 
     @property
     def built(self):
@@ -152,6 +184,11 @@ class FusedAdamW(torch.optim.Optimizer):
         (they live, up to date, on the ranks that own them).  A step may also be taken slice by slice as the slices'
         gradients arrive (GradReducer.reduce_flat_and_step): advance=True on the first call only (the step count moves
         once), loose=True on one call only (parameters outside the flat buffer)."""
+        ema, ema_warm = self._ema_opts()
+        if ema is not None and self.shard_exchange is not None:
+            raise ValueError(NO_EMA_SHARDED)
+        if self._ema_in:
+            raise RuntimeError(EMA_IN.format("step()"))
         if self.windowed:         # grad_acc_batch > 1 or max_grad_norm: the step goes through the window
             if shards is not None or not (advance and loose) or self.shard_exchange is not None:
                 raise ValueError(NO_EXCHANGE)
@@ -162,12 +199,17 @@ class FusedAdamW(torch.optim.Optimizer):
         lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
         if not self.built:
             self._build()
+        self._ensure_ema()
         if advance:
             self._flat_step += 1
             self._step_dev += 1            # device-side copy: a captured step keeps counting under graph replay
             self._sparse_zero_bookkeeping()
         for off, k in ([(0, self.flat_p.numel())] if shards is None else shards):
-            if k > 0:
+            if k > 0 and ema is not None:      # (elementwise: the average moves slice by slice with the parameters)
+                ops.adamw_ema_(self.flat_p[off:off + k], self.flat_g[off:off + k], self.flat_m[off:off + k],
+                               self.flat_v[off:off + k], self.flat_ema[off:off + k], ema, ema_warm, lr, b1, b2, eps, wd,
+                               self._flat_step, self._step_dev)
+            elif k > 0:
                 ops.adamw_(self.flat_p[off:off + k], self.flat_g[off:off + k], self.flat_m[off:off + k], self.flat_v[off:off + k],
                            lr, b1, b2, eps, wd, self._flat_step, self._step_dev)
         if not loose:
@@ -186,6 +228,10 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
             st["step"] += 1
             gr = p.grad.float().contiguous()
+            if ema is not None:
+                ops.adamw_ema_(p.data.view(-1), gr.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
+                               self._loose_average(p), ema, ema_warm, lr, b1, b2, eps, wd, st["step"])
+                continue
             ops.adamw_(p.data.view(-1), gr.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps,
                        wd, st["step"])
 
@@ -227,6 +273,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if not self.built:
             self._build()
         self._ensure_window_buffers()
+        self._ensure_ema()
         self._sparse_zero_bookkeeping()
         apply = self._pending + 1 >= K
         nb = None
@@ -253,7 +300,10 @@ class FusedAdamW(torch.optim.Optimizer):
         nothing is pending."""
         if self._pending == 0:
             return
+        if self._ema_in:
+            raise RuntimeError(EMA_IN.format("flush()"))
         K, mx = self._window_opts()
+        self._ensure_ema()
         with torch.no_grad():
             self._apply(K, mx, None)
 
@@ -278,8 +328,13 @@ class FusedAdamW(torch.optim.Optimizer):
                 extra = self._extra_dev
         self._flat_step += 1
         self._step_dev += 1                # once per applied update (torch's step count under the usual accumulation idiom)
-        ops.adamw_ex_(self.flat_p, src, self.flat_m, self.flat_v, lr, b1, b2, eps, wd, self._flat_step, self._step_dev,
-                      count_dev, partials, n_part, extra, mx or 0.0, norm_out)
+        ema, ema_warm = self._ema_opts()   # the average moves here, on the applying update, never on a micro-batch
+        if ema is not None:
+            ops.adamw_ema_(self.flat_p, src, self.flat_m, self.flat_v, self.flat_ema, ema, ema_warm, lr, b1, b2, eps, wd,
+                           self._flat_step, self._step_dev, count_dev, partials, n_part, extra, mx or 0.0, norm_out)
+        else:
+            ops.adamw_ex_(self.flat_p, src, self.flat_m, self.flat_v, lr, b1, b2, eps, wd, self._flat_step, self._step_dev,
+                          count_dev, partials, n_part, extra, mx or 0.0, norm_out)
         ops.ZeroArena.end_step()           # (behind the sweep, as in step_shards)
         for p, a in loose_src:
             st = self.state[p]
@@ -288,6 +343,11 @@ class FusedAdamW(torch.optim.Optimizer):
                 st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
                 st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
             st["step"] += 1
+            if ema is not None:
+                ops.adamw_ema_(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), self._loose_average(p),
+                               ema, ema_warm, lr, b1, b2, eps, wd, st["step"], None, count_dev, partials, n_part, extra,
+                               mx or 0.0, None)
+                continue
             ops.adamw_ex_(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps, wd,
                           st["step"], None, count_dev, partials, n_part, extra, mx or 0.0, None)
         if acc_mode:
@@ -297,6 +357,118 @@ class FusedAdamW(torch.optim.Optimizer):
             self._loose_live.clear()
         self._pending = 0
         self.last_grad_norm = norm_out
+
+    # -- weight EMA ------------------------------------------------------------------------
+    def _ema_opts(self):
+        g = self.param_groups[0]
+        d, w = g.get("ema_decay"), g.get("ema_warmup", False)
+        _check_ema_opts(d, w)
+        return (None if d is None else float(d)), bool(w)
+
+    @property
+    def averaging(self):
+        """ema_decay is set: every applied update goes through coma_adamw_ema."""
+        return self._ema_opts()[0] is not None
+
+    def _ensure_ema(self):
+        """The average of the flat buffer, allocated and started at the parameters' values (e_0 = p_0) outside any graph
+        capture: when the layout is built, or at the first step after the option was switched on.  Averages that
+        load_ema_state_dict parked before the layout existed move in here."""
+        if not self.built or not self.averaging:
+            return
+        if self.flat_ema is None:
+            self.flat_ema = self.flat_p.clone()
+        for p, t in list(self._ema_parked.items()):
+            t = t.to(self.flat_p.device).float().reshape(-1)
+            if id(p) in self._flat_ids:
+                off, k = self._offsets[id(p)]
+                self.flat_ema[off:off + k].copy_(t)
+            elif id(p) in self._dynamic:          # (a parameter that never receives a gradient has no average)
+                self._loose_ema[p] = t.clone()
+        self._ema_parked.clear()
+
+    def _loose_average(self, p):
+        """The average of a parameter outside the flat buffer: starts at its value when it is first stepped."""
+        e = self._loose_ema.get(p)
+        if e is None:
+            e = self._loose_ema[p] = p.data.detach().float().reshape(-1).clone()
+        return e
+
+    def reset_ema(self):
+        """Restart the average from the parameters' current values."""
+        if self._ema_in:
+            raise RuntimeError(EMA_IN.format("reset_ema()"))
+        self._ema_parked.clear()
+        self._loose_ema.clear()
+        if self.flat_ema is not None:
+            self.flat_ema.copy_(self.flat_p)
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange parameters and average BY CONTENT (coma_swap_f32 on the flat buffers and on every parameter outside them
+        that has an average): `p.data`, the flat views and the addresses a captured graph holds all stay where they are.
+        Call it again to swap back.  While the average is in, step(), flush() and state_dict() raise RuntimeError."""
+        if not self.averaging:
+            raise RuntimeError("swap_ema(): this optimizer keeps no average (ema_decay is None)")
+        if self._pending:
+            raise RuntimeError(f"swap_ema(): {self._pending} micro-batch(es) of an open accumulation window -- call flush() first")
+        self._ensure_ema()
+        if self.flat_ema is not None:         # (before the first step the average IS the parameters: nothing to move)
+            ops.swap_f32_(self.flat_p, self.flat_ema)
+        for p, e in self._loose_ema.items():
+            ops.swap_f32_(p.data.view(-1), e)
+        self._ema_in = not self._ema_in
+
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` -- the model computes with the averaged weights inside, with the iterate again
+        after it (also when the body raises)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            self.swap_ema()
+            try:
+                yield self
+            finally:
+                self.swap_ema()
+        return scope()
+
+    def _average_of(self, p):
+        """The average of parameter p as a tensor of its shape, or None where there is none."""
+        if self.built and id(p) in self._flat_ids and self.flat_ema is not None:
+            off, k = self._offsets[id(p)]
+            return (self.flat_p if self._ema_in else self.flat_ema)[off:off + k].view(p.shape)
+        if p in self._loose_ema:
+            return (p.data if self._ema_in else self._loose_ema[p]).view(p.shape)
+        if p in self._ema_parked:
+            return self._ema_parked[p].view(p.shape)
+        return None
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` with the averaged values where an average exists; everything else -- parameters that never
+        received a gradient and all buffers, BatchNorm running statistics included -- as it is now
+        (``AveragedModel(use_buffers=False)``).  Loads into a model with ``load_state_dict``."""
+        if not self.averaging:
+            raise RuntimeError("ema_state_dict(): this optimizer keeps no average (ema_decay is None)")
+        self._ensure_ema()
+        sd = model.state_dict()
+        for name, p in model.named_parameters():
+            avg = self._average_of(p)
+            if name in sd and avg is not None:
+                sd[name] = avg.detach().to(sd[name].dtype).clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, model, sd):
+        """Restore the averages from an ``ema_state_dict``.  Before the flat layout exists they wait, like the moments of
+        load_state_dict, and _build() moves them in."""
+        if self._ema_in:
+            raise RuntimeError(EMA_IN.format("load_ema_state_dict()"))
+        for name, p in model.named_parameters():
+            if name in sd:
+                self._ema_parked[p] = sd[name].detach().to(p.device).float().clone()
+        self._ensure_ema()
 
     def _sparse_zero_bookkeeping(self):
         """After a backward: (1) any large tensor zero_grad() skipped that the kernels did NOT overwrite this step still
@@ -336,6 +508,8 @@ class FusedAdamW(torch.optim.Optimizer):
         """torch.optim.AdamW's format.  Under a sharded exchange the moments of this rank's sub-slices are current and the
         others stopped at the last unsharded step: they are all-gathered first (every rank must call state_dict(), like any
         collective; afterwards every rank holds the full, identical state)."""
+        if self._ema_in:
+            raise RuntimeError(EMA_IN.format("state_dict()"))
         if self._pending:
             raise RuntimeError(f"FusedAdamW.state_dict(): {self._pending} micro-batch(es) of an open accumulation window are "
                                "not applied yet -- call flush() first")
@@ -359,8 +533,10 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         params = self.param_groups[0]["params"]
+        # (a file written without an average does not switch off the one this optimizer was built with)
+        skip = ("params", "ema_decay", "ema_warmup") if sd["param_groups"][0].get("ema_decay") is None else ("params",)
         for k, v in sd["param_groups"][0].items():
-            if k != "params":
+            if k not in skip:
                 self.param_groups[0][k] = v
         # the flat layout exists only after the first backward: until then the moments wait in self.state[p]
         # (per-parameter AdamW entries) and _build() moves them into the flat buffers

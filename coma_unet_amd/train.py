@@ -14,15 +14,18 @@ from .optim import FusedAdamW, check_no_exchange
 from .data_parallel import GradReducer, StreamedGradExchange
 
 
-def make_optimizer(model, lr=1e-3, write_through=True, pad_to=1, grad_acc_batch=1, max_grad_norm=None):
+def make_optimizer(model, lr=1e-3, write_through=True, pad_to=1, grad_acc_batch=1, max_grad_norm=None, ema_decay=None,
+                   ema_warmup=False):
     """torch.optim.AdamW(model.parameters(), lr) of :736, fused.  ``write_through``: parameter gradients are
     written by the backward kernels straight into the optimizer's flat gradient buffer (see ops.GradSink).
     ``pad_to``: the world size when the step is sharded over ranks (StreamedGradExchange(sharded=True)).
     ``grad_acc_batch`` / ``max_grad_norm``: one update per grad_acc_batch steps with the mean of their gradients, clipped
-    to that global norm (optim.FusedAdamW; the reference's commented-out accumulation, :887-890, :918-920)."""
+    to that global norm (optim.FusedAdamW; the reference's commented-out accumulation, :887-890, :918-920).
+    ``ema_decay`` / ``ema_warmup``: an exponential moving average of the weights kept by the update's own kernel
+    (``optimizer.ema_weights()``, ``ema_state_dict``)."""
     dyn = [model.pos_dynamic_prompt, model.neg_dynamic_prompt] if not getattr(model, "static_prompts", False) else []
     return FusedAdamW(model.parameters(), lr=lr, dynamic=dyn, write_through=write_through, pad_to=pad_to,
-                      grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm)
+                      grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
 
 def forward_loss(model, criterion, batch, global_rnc=False):
@@ -109,7 +112,7 @@ class GraphedTrainStep:
     def _hyper(self):
         g = self.optimizer.param_groups[0]
         return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), g.get("grad_acc_batch", 1),
-                g.get("max_grad_norm"))
+                g.get("max_grad_norm"), g.get("ema_decay"), bool(g.get("ema_warmup", False)))
 
     def _capture(self):
         """(Re)capture.  The optimizer's hyper-parameters are kernel arguments frozen into the graph, so a change of
@@ -122,6 +125,7 @@ class GraphedTrainStep:
             self.watch = reducer.graph_watch(self.batch["mri"].device)
         self.graph = torch.cuda.CUDAGraph()
         self.micro_graph = None
+        optimizer._ensure_ema()          # (ema_decay switched on since the last step: the average is allocated out here)
         K = int(optimizer.param_groups[0].get("grad_acc_batch", 1))
         if K > 1:
             return self._capture_window(K)

@@ -17,6 +17,7 @@ Differences that are interface, not arithmetic:
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import os
@@ -27,7 +28,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from . import metrics as M
 from .checkpoint import save_checkpoint
-from .optim import NO_EXCHANGE, check_no_exchange
+from .optim import NO_EMA_SHARDED, NO_EXCHANGE, check_no_exchange
 from .train import make_optimizer, train_step, GraphedTrainStep
 
 
@@ -105,6 +106,12 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        clipped to that global norm.  A window still open at the end of an epoch is applied there (``optimizer.flush()``,
        the reference's "ensure BP on the remaining accumulated batches", :918-920), before the scheduler step and the
        checkpoint.  Not available together with ``reducer`` (ValueError).
+     * ``ema_decay`` / ``ema_warmup`` / ``ema_eval`` (None / False / True): ``ema_decay`` and ``ema_warmup`` are passed to
+       ``make_optimizer`` when the optimizer is built here -- an exponential moving average of the weights, kept by the
+       update's own kernel (optim.FusedAdamW).  With ``ema_eval`` the validation / in-sample ``contrastive_test`` passes run
+       under the averaged weights (``optimizer.ema_weights()``: swapped in by content and back out, BatchNorm running
+       statistics stay the iterate's); a ``predictor=`` passed through is ``refresh()``ed inside and again after.  Every
+       checkpoint carries the average as ``"ema_state_dict"``.  Not available under a sharded exchange (ValueError).
      * ``freeze_bn``: when given, ``model.freeze_batchnorm(freeze_bn)`` before the first epoch (else the model stays as
        the caller set it) -- every BatchNorm3d normalises with its running statistics and leaves them alone (fine-tuning
        a resumed checkpoint); the switch survives the ``model.train(True)`` of every epoch."""
@@ -140,11 +147,14 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
         elif reducer is not None:
             optimizer = reducer.opt           # the reducer buckets THIS optimizer's flat gradient buffer
         else:
-            optimizer = make_optimizer(model, lr, grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm)
+            optimizer = make_optimizer(model, lr, grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm,
+                                       ema_decay=kwargs.get("ema_decay"), ema_warmup=kwargs.get("ema_warmup", False))
         for g in optimizer.param_groups:
             g["lr"] = lr
         scheduler = ReduceLROnPlateau(optimizer, "min", patience=5)
     check_no_exchange(optimizer, reducer)
+    if getattr(optimizer, "averaging", False) and getattr(optimizer, "shard_exchange", None) is not None:
+        raise ValueError(NO_EMA_SHARDED)
     if reducer is not None:
         assert reducer.opt is optimizer, "train_dp(reducer=...) must step the optimizer the reducer was built on"
     use_graph = kwargs.get("graph", "auto")
@@ -156,7 +166,6 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     # graph mode: the whole loop runs on a side stream, like GraphedTrainStep's own warm-up -- the eager steps that precede
     # the capture must not have run on the (legacy) default stream (torch.cuda.graph's documented requirement; a capture
     # right behind default-stream steps crashed in capture_end on ROCm 7.2)
-    import contextlib
     scope = contextlib.ExitStack()
     if use_graph and device.type == "cuda":
         side = torch.cuda.Stream(device=device)
@@ -179,6 +188,7 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
                             "roi_corrs", "roi_rses")}
     best_mape, best_avg_corr = float("inf"), -float("inf")
     loss = None
+    ema_eval = bool(kwargs.get("ema_eval", True)) and getattr(optimizer, "averaging", False)
     for epoch in range(start_epoch, epochs):
         model.train(True)
         epoch_loss, num_samples = 0.0, 0
@@ -237,7 +247,7 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
             # every rank assembles the dict (FusedAdamW.state_dict() all-gathers sharded moments), rank 0 writes it
             save_checkpoint(save_path, epoch, model, optimizer, loss, scheduler, checkpoint_iter=checkpoint_iter, write=rank == 0)
         if epoch % val_iter == 0 and validation_loader is not None and rank == 0:                         # :957-1017
-            with torch.no_grad():
+            with torch.no_grad(), _eval_weights(optimizer, ema_eval, kwargs.get("predictor")):
                 val_save = os.path.join(save_path, f"{epoch}_output_samples") if save_path else ""
                 if val_save:
                     os.makedirs(val_save, exist_ok=True)
@@ -257,7 +267,7 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
                 best_avg_corr = float(np.nanmean(roi_corr))
                 logging.info(f"Highest ROI Averaged Correlations so far: Epoch {epoch}")
         if epoch != 0 and epoch > 29 and epoch % overfit_val_iter == 0 and rank == 0:                     # :1019-1034
-            with torch.no_grad():
+            with torch.no_grad(), _eval_weights(optimizer, ema_eval, kwargs.get("predictor")):
                 res = contrastive_test(model, train_loader, criterion.gen_loss.roi_indices, criterion.gen_loss.roi_weights,
                                        save_path="", cuda_id=cuda_id, pred_sample_file=pred_sample_file,
                                        with_train_loader=not kwargs.get("with_test_loader", False), in_sample_test=True, **kwargs)
@@ -267,6 +277,23 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
         if world > 1:
             dist.barrier()          # ranks 1.. wait for rank 0's validation before the next epoch's first collective
     return epoch_avg_losses
+
+
+@contextlib.contextmanager
+def _eval_weights(optimizer, ema_eval, predictor=None):
+    """The evaluation passes of train_dp: under the averaged weights when ``ema_eval`` (optimizer.ema_weights()).  A Predictor
+    folds parameters into tables of its own, so it is refreshed once the average is in and again once the iterate is back."""
+    if not ema_eval:
+        yield
+        return
+    try:
+        with optimizer.ema_weights():
+            if predictor is not None:
+                predictor.refresh()
+            yield
+    finally:
+        if predictor is not None:
+            predictor.refresh()
 
 
 def print_metrics(criterion, mae, mape, rse, rrmse, ssim_error, roi_maes, roi_mapes, roi_rses, roi_wrrmses, roi_correlations,

@@ -442,6 +442,27 @@ int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64_t n, float
                   const int32_t* count_dev, const double* partials, int32_t n_partials,
                   const double* extra_sumsq, float max_norm, float* norm_out, void* stream);
 
+/* ---- exponential moving average of the weights inside the same sweep (FusedAdamW(ema_decay, ema_warmup)).
+ * coma_adamw_ema: coma_adamw_ex with the same arguments (p, m, v come out bitwise the same; with count_dev == NULL and
+ *   partials == NULL bitwise coma_adamw's), then, per element, on the parameter p' just computed
+ *       e' = fmaf(1 - d_t, p' - e, e)                      (torch's get_ema_multi_avg_fn: lerp(e, p', 1 - d))
+ *   stored to ema (length n, fp32).  d_t is formed in fp32 on the device:
+ *       ema_warmup == 0:  d_t = ema_decay
+ *       otherwise:        d_t = min(ema_decay, (1 + t) / (10 + t)),  t = *step_dev when step_dev is non-NULL, else step
+ *   (the update count, from 1: a replayed graph moves through the warm-up).  ema_decay must lie strictly inside (0, 1).
+ *   The caller starts the average at the parameters' values (e_0 = p_0).  fp32 limit: an increment (1 - d)|p' - e| below
+ *   half an ulp of e is lost.  16-byte accesses where all five buffers are 16-byte aligned, scalar otherwise.
+ *   n == 0: no launch. ---- */
+int coma_adamw_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                   const int32_t* count_dev, const double* partials, int32_t n_partials,
+                   const double* extra_sumsq, float max_norm, float* norm_out, float* ema, float ema_decay,
+                   int32_t ema_warmup, void* stream);
+/* coma_swap_f32: exchange the CONTENTS of two disjoint device buffers of n floats (a[i] <-> b[i]); the addresses that
+ *   parameter views and captured graphs hold stay valid.  a == b or overlapping ranges: error status, nothing launched.
+ *   Same 16-byte / scalar paths as coma_adamw_ema.  n == 0: no launch. */
+int coma_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* ---- 3-D SSIM (MONAI SSIMMetric(spatial_dims=3), attn_unet_data_parallel.py:1176,1234) ----
  * x, y: single-channel volumes; window: `win` (<= 11) separable weights (host pointer); c1 = (k1 R)^2, c2 = (k2 R)^2.
  * Writes one fp64 partial sum of the SSIM map per 8^3 output tile: partial[b * ntiles + t]; the per-sample SSIM is
