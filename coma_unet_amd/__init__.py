@@ -8,7 +8,7 @@ from .attn_unet_data_parallel import (ContrastiveAttentionUNET_DP, ObservableAtt
                                       ObservableAttentionBlock, UpBlock, ProjectionHead, StackedFusionConvLayers)
 from .inference import Predictor, fold_gate
 from .optim import FusedAdamW
-from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, build_reference_criterion
+from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
 DEFAULT_MODEL_PARAMS = (3, 1, 1, [32, 64, 128, 256, 512], [2] * 5)   # validation.py:727
 

@@ -125,6 +125,74 @@ class VoxelL1(nn.Module):
         return torch.mean(loss) if self.batch_reduction == "mean" else loss
 
 
+class SSIMLoss(nn.Module):
+    """1 - SSIM per sample, differentiable in `pred` (the value is 1 - metrics.ssim3d; the constructor is
+    monai.losses.SSIMLoss's without spatial_dims).  The target is a label and gets no gradient."""
+
+    MAX_WIN = 11        # SSIM_MAXW of csrc/metrics.hip
+
+    def __init__(self, data_range=1.0, kernel_type="gaussian", win_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03, reduction="mean"):
+        super().__init__()
+        from .metrics import ssim_window
+        if int(win_size) != win_size or not 1 <= win_size <= self.MAX_WIN:
+            raise ValueError(f"SSIMLoss: win_size must be an integer in 1..{self.MAX_WIN}, got {win_size}")
+        if kernel_type not in ("gaussian", "uniform"):
+            raise ValueError(f"SSIMLoss: kernel_type must be 'gaussian' or 'uniform', got {kernel_type!r}")
+        if reduction not in ("mean", None):
+            raise ValueError(f"SSIMLoss: reduction must be 'mean' or None, got {reduction!r}")
+        if not float(data_range) > 0 or (kernel_type == "gaussian" and not float(kernel_sigma) > 0):
+            raise ValueError("SSIMLoss: data_range and kernel_sigma must be positive")
+        self.win_size = int(win_size)
+        self.window = ssim_window(kernel_type, self.win_size, kernel_sigma)
+        self.c1, self.c2 = (k1 * float(data_range)) ** 2, (k2 * float(data_range)) ** 2
+        self.batch_reduction = reduction
+
+    def forward(self, pred, gt, roi=None):
+        if pred.dim() != 5 or pred.shape[1] != 1 or pred.shape != gt.shape:
+            raise ValueError(f"SSIMLoss: (B, 1, D, H, W) volumes of equal shape expected, got {tuple(pred.shape)}, {tuple(gt.shape)}")
+        if min(pred.shape[2:]) < self.win_size:
+            raise ValueError(f"SSIMLoss: volume {tuple(pred.shape[2:])} is smaller than the {self.win_size}-wide window")
+        p = _vol_internal(pred)
+        loss = ops.SSIMLoss.apply(p, _vol_internal(gt.detach(), p.dtype).contiguous(), self.window, self.c1, self.c2)   # (B, 1)
+        return torch.mean(loss) if self.batch_reduction == "mean" else loss
+
+
+class WithSSIM(nn.Module):
+    """A generative loss plus an SSIM term: base(pred, gt, roi) + ssim_weight * (1 - ssim_b) -- per sample while
+    `batch_reduction` is None, else the batch mean of both.  `batch_reduction` IS the base loss's (one shared attribute),
+    and everything the training loop reads from `criterion.gen_loss` (ROI tables, weight updates) is the base loss's."""
+
+    _BASE_ATTRS = ("batch_reduction", "roi_indices", "roi_weights", "voxel_wise", "voxel_weights", "scale_factor")
+    _BASE_METHODS = ("calculate_new_weights", "calculate_new_voxel_weights", "update_weights")
+
+    def __init__(self, base, ssim_weight, **ssim_kwargs):
+        super().__init__()
+        if not hasattr(base, "batch_reduction"):
+            raise ValueError("WithSSIM: base must be a generative loss with a batch_reduction attribute")
+        w = float(ssim_weight)
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError(f"WithSSIM: ssim_weight must be a finite number >= 0, got {ssim_weight}")
+        self.base = base
+        self.ssim_weight = w
+        self.ssim = SSIMLoss(**dict(ssim_kwargs, reduction=None))
+
+    def __getattr__(self, name):
+        if name in WithSSIM._BASE_ATTRS or name in WithSSIM._BASE_METHODS:
+            return getattr(super().__getattr__("base"), name)
+        return super().__getattr__(name)
+
+    def __setattr__(self, name, value):
+        if name in WithSSIM._BASE_ATTRS:
+            setattr(self.base, name, value)
+        else:
+            super().__setattr__(name, value)
+
+    def forward(self, pred, gt, roi=None):
+        loss = self.base(pred, gt, roi)
+        s = self.ssim(pred, gt)                                    # (B, 1)
+        return loss + self.ssim_weight * (s if self.batch_reduction is None else torch.mean(s))
+
+
 class LabelDifference(nn.Module):
     def __init__(self, distance_type="l1"):
         super().__init__()

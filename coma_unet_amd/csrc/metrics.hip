@@ -149,9 +149,12 @@ struct SsimP {
   float c1, c2;
   float w[SSIM_MAXW];
   double* partial;      // [B][ntiles]
+  float* coef;          // COEF only: dS/dm0, dS/dm2, dS/dm4 per valid output voxel, planar [3][B][Do][Ho][Wo]
 };
 
-template <typename T>
+// COEF = false is the metric kernel.  COEF = true (the training loss, coma_ssim_fwd_coef) also stores the three
+// coefficient maps the backward kernel ssim_bwd_k convolves; the sums are the same instructions either way.
+template <typename T, bool COEF = false>
 __global__ __launch_bounds__(256) void ssim_partial_k(SsimP p) {
   constexpr int TO = SSIM_T, TI = SSIM_T + SSIM_MAXW - 1;       // outputs / inputs per axis (input extent used: TO + win - 1)
   __shared__ float in_[2][TI][TI][TI];                          // x, y cubes                        (2 * 18^3 * 4 = 46.7 KB)
@@ -210,6 +213,16 @@ __global__ __launch_bounds__(256) void ssim_partial_k(SsimP p) {
       const float sx = m[2] - m[0] * m[0], sy = m[3] - m[1] * m[1], sxy = m[4] - m[0] * m[1];
       const float cs = (2.f * sxy + p.c2) / (sx + sy + p.c2);
       acc += (double)(((2.f * m[0] * m[1] + p.c1) / (m[0] * m[0] + m[1] * m[1] + p.c1)) * cs);
+      if constexpr (COEF) {
+        const float B1 = m[0] * m[0] + m[1] * m[1] + p.c1, B2 = sx + sy + p.c2;
+        const float Lm = (2.f * m[0] * m[1] + p.c1) / B1;
+        const int64_t plane = (int64_t)Do * Ho * Wo;
+        float* cf = p.coef + (int64_t)b * plane + ((int64_t)(z0 + oz) * Ho + (y0 + oy)) * Wo + (x0 + ox);
+        const int64_t qs = (int64_t)gridDim.y * plane;
+        cf[0] = 2.f * cs * (m[1] - m[0] * Lm) / B1 + 2.f * Lm * (m[0] * cs - m[1]) / B2;
+        cf[qs] = -Lm * cs / B2;
+        cf[2 * qs] = 2.f * Lm / B2;
+      }
     }
   }
   red[tid] = acc;
@@ -236,12 +249,155 @@ extern "C" int coma_ssim_partial(const coma_tensor* x, const coma_tensor* y, con
   p.D = x->D; p.H = x->H; p.W = x->W; p.win = win; p.c1 = c1; p.c2 = c2;
   for (int k = 0; k < SSIM_MAXW; ++k) p.w[k] = k < win ? window[k] : 0.f;
   p.ntz = (x->D - win + SSIM_T) / SSIM_T; p.nty = (x->H - win + SSIM_T) / SSIM_T; p.ntx = (x->W - win + SSIM_T) / SSIM_T;
-  p.partial = partial;
+  p.partial = partial; p.coef = nullptr;
   const int nt = p.ntx * p.nty * p.ntz;
   *ntiles_out = nt;
   dim3 grid((unsigned)nt, (unsigned)x->B);
   if (x->dtype == COMA_F32) hipLaunchKernelGGL(ssim_partial_k<float>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(ssim_partial_k<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// SSIM as a training loss (DESIGN.md section 4 "SSIM loss").  With m0..m4 the windowed means of x, y, x^2, y^2, xy and
+// S = L * C the SSIM map, dS/dx[v] = (W^T a0)[v] + 2 x[v] (W^T a2)[v] + y[v] (W^T a4)[v] where a0 = dS/dm0, a2 = dS/dm2,
+// a4 = dS/dm4 and W^T is the adjoint of the "valid" separable window: (W^T a)[v] = sum_k w[k] a[v - k] per axis, a = 0
+// outside the valid output range.  The forward kernel (COEF = true) stores a0, a2, a4; ssim_bwd_k gives one block an 8^3
+// tile of INPUT voxels, stages the (8 + win - 1)^3 cube of one map at a time in LDS, runs the three adjoint passes there
+// and accumulates the three results per voxel in registers.  Each dx voxel has one owner: no atomics, bitwise repeatable.
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" size_t coma_ssim_coef_bytes(const coma_tensor* x, int32_t win) {
+  if (!x || win < 1 || win > SSIM_MAXW || x->D < win || x->H < win || x->W < win) return 0;
+  return (size_t)3 * x->B * (x->D - win + 1) * (x->H - win + 1) * (x->W - win + 1) * sizeof(float);
+}
+
+extern "C" int coma_ssim_fwd_coef(const coma_tensor* x, const coma_tensor* y, const float* window, int32_t win, float c1, float c2,
+                                  double* partial, size_t partial_bytes, int32_t* ntiles_out, float* coef, size_t coef_bytes,
+                                  void* stream) {
+  COMA_CHECK(x && y && x->data && y->data && window && partial && ntiles_out && coef, "ssim_fwd_coef: null argument");
+  COMA_CHECK(t_same_grid(x, y) && x->C == 1 && y->C == 1 && x->dtype == y->dtype,
+             "ssim_fwd_coef: single-channel volumes of equal shape and dtype expected");
+  COMA_CHECK(win >= 1 && win <= SSIM_MAXW && x->D >= win && x->H >= win && x->W >= win, "ssim_fwd_coef: window %d does not fit", win);
+  COMA_CHECK(partial_bytes >= coma_ssim_ws_bytes(x, win), "ssim_fwd_coef: partial buffer too small");
+  COMA_CHECK(coef_bytes >= coma_ssim_coef_bytes(x, win), "ssim_fwd_coef: coefficient buffer too small");
+  SsimP p;
+  p.x = x->data; p.ldx = x->ld; p.sbx = x->sb; p.y = y->data; p.ldy = y->ld; p.sby = y->sb;
+  p.D = x->D; p.H = x->H; p.W = x->W; p.win = win; p.c1 = c1; p.c2 = c2;
+  for (int k = 0; k < SSIM_MAXW; ++k) p.w[k] = k < win ? window[k] : 0.f;
+  p.ntz = (x->D - win + SSIM_T) / SSIM_T; p.nty = (x->H - win + SSIM_T) / SSIM_T; p.ntx = (x->W - win + SSIM_T) / SSIM_T;
+  p.partial = partial; p.coef = coef;
+  const int nt = p.ntx * p.nty * p.ntz;
+  *ntiles_out = nt;
+  dim3 grid((unsigned)nt, (unsigned)x->B);
+  if (x->dtype == COMA_F32) hipLaunchKernelGGL((ssim_partial_k<float, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((ssim_partial_k<bf16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+
+struct SsimBwdP {
+  const void* x; int64_t ldx, sbx;
+  const void* y; int64_t ldy, sby;
+  void* dx; int64_t ldd, sbd;
+  const float* coef;    // [3][B][Do][Ho][Wo]
+  const float* gout;    // [B], device
+  int D, H, W, win;
+  int ntx, nty;
+  float inv_n;          // 1 / N_valid
+  float w[SSIM_MAXW];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ssim_bwd_k(SsimBwdP p) {
+  constexpr int TO = SSIM_T, TI = SSIM_T + SSIM_MAXW - 1;       // dx voxels / coefficient voxels per axis (used: TO + win - 1)
+  __shared__ float cube[TI][TI][TI];                            // one coefficient map                (18^3 * 4 = 23.3 KB)
+  __shared__ float px[TI][TI][TO];                              // after the x pass                   (10.4 KB)
+  __shared__ float py[TI][TO][TO];                              // after the y pass                   (4.6 KB)
+  const int b = blockIdx.y;
+  int t = blockIdx.x;
+  const int tx = t % p.ntx; t /= p.ntx;
+  const int ty = t % p.nty; const int tz = t / p.nty;
+  const int x0 = tx * TO, y0 = ty * TO, z0 = tz * TO;           // first dx voxel of the tile
+  const int h = p.win - 1, ext = TO + h;
+  const int Do = p.D - h, Ho = p.H - h, Wo = p.W - h;
+  const int64_t plane = (int64_t)Do * Ho * Wo;
+  const int tid = threadIdx.x;
+  // the two dx voxels this thread owns: (vx, vy, vz[j])
+  const int vx = tid % TO, vy = (tid / TO) % TO, vz0 = tid / (TO * TO);
+  float xv[2] = {0.f, 0.f}, yv[2] = {0.f, 0.f}, acc[2] = {0.f, 0.f};
+  bool in[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int gx = x0 + vx, gy = y0 + vy, gz = z0 + vz0 + 4 * j;
+    in[j] = gx < p.W && gy < p.H && gz < p.D;
+    if (in[j]) {
+      const int64_t v = ((int64_t)gz * p.H + gy) * p.W + gx;
+      xv[j] = ld_f(reinterpret_cast<const T*>(p.x) + (int64_t)b * p.sbx + v * p.ldx);
+      yv[j] = ld_f(reinterpret_cast<const T*>(p.y) + (int64_t)b * p.sby + v * p.ldy);
+    }
+  }
+  for (int q = 0; q < 3; ++q) {
+    // coefficient voxel `l` of the cube is output voxel (tile origin - h + l): dx[v] sums outputs v - h .. v
+    const float* cq = p.coef + ((int64_t)q * gridDim.y + b) * plane;
+    for (int i = tid; i < ext * ext * ext; i += 256) {
+      const int lx = i % ext, ly = (i / ext) % ext, lz = i / (ext * ext);
+      const int ox = x0 - h + lx, oy = y0 - h + ly, oz = z0 - h + lz;
+      float a = 0.f;
+      if (ox >= 0 && ox < Wo && oy >= 0 && oy < Ho && oz >= 0 && oz < Do) a = cq[((int64_t)oz * Ho + oy) * Wo + ox];
+      cube[lz][ly][lx] = a;
+    }
+    __syncthreads();
+    for (int i = tid; i < ext * ext * TO; i += 256) {           // x pass: dx voxel ix takes w[k] from output ix - k
+      const int ix = i % TO, ly = (i / TO) % ext, lz = i / (TO * ext);
+      float s = 0.f;
+      for (int k = 0; k < p.win; ++k) s = fmaf(p.w[k], cube[lz][ly][ix + h - k], s);
+      px[lz][ly][ix] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < ext * TO * TO; i += 256) {            // y pass
+      const int ix = i % TO, iy = (i / TO) % TO, lz = i / (TO * TO);
+      float s = 0.f;
+      for (int k = 0; k < p.win; ++k) s = fmaf(p.w[k], px[lz][iy + h - k][ix], s);
+      py[lz][iy][ix] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {                               // z pass + combine
+      const int iz = vz0 + 4 * j;
+      float s = 0.f;
+      for (int k = 0; k < p.win; ++k) s = fmaf(p.w[k], py[iz + h - k][vy][vx], s);
+      acc[j] = fmaf(q == 0 ? 1.f : (q == 1 ? 2.f * xv[j] : yv[j]), s, acc[j]);
+    }
+    // the next map's passes overwrite cube / px / py only behind barriers that follow their last reads above
+  }
+  const float scale = p.gout[b] * p.inv_n;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (!in[j]) continue;
+    const int64_t v = ((int64_t)(z0 + vz0 + 4 * j) * p.H + (y0 + vy)) * p.W + (x0 + vx);
+    st_f(reinterpret_cast<T*>(p.dx) + (int64_t)b * p.sbd + v * p.ldd, scale * acc[j]);
+  }
+}
+
+extern "C" int coma_ssim_bwd(const coma_tensor* x, const coma_tensor* y, const float* coef, const float* window, int32_t win,
+                             const float* gout, const coma_tensor* dx, void* stream) {
+  COMA_CHECK(x && y && dx && x->data && y->data && dx->data && coef && window && gout, "ssim_bwd: null argument");
+  COMA_CHECK(t_same_grid(x, y) && t_same_grid(x, dx) && x->C == 1 && y->C == 1 && dx->C == 1 && x->dtype == y->dtype &&
+             x->dtype == dx->dtype, "ssim_bwd: single-channel volumes of equal shape and dtype expected");
+  COMA_CHECK(win >= 1 && win <= SSIM_MAXW && x->D >= win && x->H >= win && x->W >= win, "ssim_bwd: window %d does not fit", win);
+  SsimBwdP p;
+  p.x = x->data; p.ldx = x->ld; p.sbx = x->sb; p.y = y->data; p.ldy = y->ld; p.sby = y->sb;
+  p.dx = dx->data; p.ldd = dx->ld; p.sbd = dx->sb;
+  p.coef = coef; p.gout = gout;
+  p.D = x->D; p.H = x->H; p.W = x->W; p.win = win;
+  for (int k = 0; k < SSIM_MAXW; ++k) p.w[k] = k < win ? window[k] : 0.f;
+  p.ntx = (x->W + SSIM_T - 1) / SSIM_T; p.nty = (x->H + SSIM_T - 1) / SSIM_T;
+  const int ntz = (x->D + SSIM_T - 1) / SSIM_T;
+  p.inv_n = (float)(1.0 / ((double)(x->D - win + 1) * (x->H - win + 1) * (x->W - win + 1)));
+  dim3 grid((unsigned)(p.ntx * p.nty * ntz), (unsigned)x->B);
+  if (x->dtype == COMA_F32) hipLaunchKernelGGL(ssim_bwd_k<float>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(ssim_bwd_k<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
   COMA_LAUNCH_CHECK();
   return 0;
 }

@@ -8,6 +8,7 @@ library on the current stream; none of them has a CPU or PyTorch fallback.
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -1489,6 +1490,41 @@ class L1Loss(Function):
         dpred = torch.empty_like(pred)
         check(lib.coma_l1_bwd(ct(pred), ct(gt), ptr(g), ct(dpred), L.stream()), "coma_l1_bwd")
         return dpred, None
+
+
+class SSIMLoss(Function):
+    """Per-sample 1 - SSIM_b (B, 1) of (B, D, H, W, 1) volumes, differentiable in `pred` (DESIGN.md section 4 "SSIM loss").
+    The forward kernel is metrics.ssim3d's with one more output: the three coefficient maps the backward kernel convolves
+    with the adjoint window -- the only thing saved besides pred and gt.  `window`: float32 numpy (host), len <= 11."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, window, c1, c2):
+        B, D, H, W, _ = pred.shape
+        win = int(window.shape[0])
+        cp = ct(pred)
+        nbytes, cbytes = lib.coma_ssim_ws_bytes(cp, win), lib.coma_ssim_coef_bytes(cp, win)
+        if not nbytes or not cbytes:
+            raise ValueError(f"SSIMLoss: volume {(D, H, W)} is smaller than the {win}-wide window")
+        part = workspace(nbytes, pred.device)[:nbytes].view(torch.float64)
+        coef = _f32(cbytes // 4, pred.device)
+        nt = ctypes.c_int32(0)
+        check(lib.coma_ssim_fwd_coef(cp, ct(gt), window.ctypes.data_as(ctypes.c_void_p), win, c1, c2, ptr(part), nbytes,
+                                     ctypes.addressof(nt), ptr(coef), cbytes, L.stream()), "coma_ssim_fwd_coef")
+        nvalid = (D - win + 1) * (H - win + 1) * (W - win + 1)
+        loss = (1.0 - part.view(B, nt.value).sum(1) / nvalid).float()      # (B, ntiles) fp64 table: tiny
+        ctx.save_for_backward(pred, gt, coef)
+        ctx.window = window
+        return loss.view(B, 1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, coef = ctx.saved_tensors
+        g = (-gout).contiguous().float().view(-1)                          # d loss_b / d ssim_b = -1
+        dpred = torch.empty_like(pred)
+        w = ctx.window
+        check(lib.coma_ssim_bwd(ct(pred), ct(gt), ptr(coef), w.ctypes.data_as(ctypes.c_void_p), int(w.shape[0]), ptr(g),
+                                ct(dpred), L.stream()), "coma_ssim_bwd")
+        return dpred, None, None, None, None
 
 
 def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, step, step_dev=None):

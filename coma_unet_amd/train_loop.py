@@ -85,6 +85,19 @@ def _same_shapes(a, b):
                                              and b[k].dtype == v.dtype) for k, v in a.items())
 
 
+def with_ssim(criterion, ssim_weight=None, ssim_kwargs=None):
+    """train_dp's ``ssim_weight`` option: wrap ``criterion.gen_loss`` in criterions.WithSSIM -- once: a loss that is already
+    wrapped (a second train_dp call on the same criterion) only takes the new weight.  None: nothing is touched."""
+    if ssim_weight is None:
+        return criterion
+    from .criterions import WithSSIM
+    if isinstance(criterion.gen_loss, WithSSIM):
+        criterion.gen_loss.ssim_weight = float(ssim_weight)
+    else:
+        criterion.gen_loss = WithSSIM(criterion.gen_loss, ssim_weight, **(ssim_kwargs or {}))
+    return criterion
+
+
 def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save_path="", cuda_id=0, pred_sample_file="",
              from_checkpoint=False, **kwargs):
     """attn_unet_data_parallel.py:696.  Returns the list of per-epoch average losses (the reference returns None; the
@@ -114,10 +127,15 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        checkpoint carries the average as ``"ema_state_dict"``.  Not available under a sharded exchange (ValueError).
      * ``freeze_bn``: when given, ``model.freeze_batchnorm(freeze_bn)`` before the first epoch (else the model stays as
        the caller set it) -- every BatchNorm3d normalises with its running statistics and leaves them alone (fine-tuning
-       a resumed checkpoint); the switch survives the ``model.train(True)`` of every epoch."""
+       a resumed checkpoint); the switch survives the ``model.train(True)`` of every epoch.
+     * ``ssim_weight`` / ``ssim_kwargs`` (None): with a weight, ``criterion.gen_loss`` is wrapped once in
+       ``criterions.WithSSIM(gen_loss, ssim_weight, **ssim_kwargs)`` -- every sample's generative loss gains
+       ``ssim_weight * (1 - SSIM_b)``, computed and differentiated by the fused SSIM kernels; the ROI tables and weight
+       updates stay the wrapped loss's.  With None the criterion is not touched and no SSIM kernel runs."""
     import torch.distributed as dist
     if "freeze_bn" in kwargs:
         model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
+    with_ssim(criterion, kwargs.get("ssim_weight"), kwargs.get("ssim_kwargs"))
     cwd = os.getcwd()
     fold = kwargs.get("fold_id")
     base = f"{cwd}/training_folds/adni_a4_first_scan_combined_folds/tau_prediction_lookups"

@@ -471,6 +471,23 @@ size_t coma_ssim_ws_bytes(const coma_tensor* x, int32_t win);
 int coma_ssim_partial(const coma_tensor* x, const coma_tensor* y, const float* window, int32_t win, float c1,
                       float c2, double* partial, size_t partial_bytes, int32_t* ntiles_out, void* stream);
 
+/* ---- SSIM as a training loss (DESIGN.md section 4 "SSIM loss"): gradient of the per-sample mean SSIM w.r.t. x ----
+ * coma_ssim_fwd_coef: coma_ssim_partial (same arguments, same partial sums) that also stores, per valid output voxel,
+ *   the three fp32 coefficient maps a0 = dS/d mu_x, a2 = dS/d E[x^2], a4 = dS/d E[xy], planar [3][B][Do][Ho][Wo]
+ *   (Do = D-win+1, ...), in `coef` (device, coma_ssim_coef_bytes(x, win) bytes; 0 = window does not fit).
+ * coma_ssim_bwd: dx (=) gout[b] / (Do Ho Wo) * (W^T a0 + 2 x W^T a2 + y W^T a4), W^T the adjoint of the "valid"
+ *   window ((W^T a)[v] = sum_k window[k] a[v - k] per axis).  gout: device fp32 [B], the upstream gradient of each
+ *   sample's mean SSIM (read on the device).  dx: grid and dtype of x; y gets no gradient.  x, y, dx may be strided
+ *   (ld, sb).  One block per 8^3 tile of dx, every voxel written by one thread: no atomics, bitwise repeatable.
+ * Both return an error status with nothing launched unless: x, y (and dx) are single-channel volumes of equal grid and
+ *   dtype, 1 <= win <= 11, the window fits the volume, and the partial / coef buffers are large enough.          */
+size_t coma_ssim_coef_bytes(const coma_tensor* x, int32_t win);
+int coma_ssim_fwd_coef(const coma_tensor* x, const coma_tensor* y, const float* window, int32_t win, float c1,
+                       float c2, double* partial, size_t partial_bytes, int32_t* ntiles_out, float* coef,
+                       size_t coef_bytes, void* stream);
+int coma_ssim_bwd(const coma_tensor* x, const coma_tensor* y, const float* coef, const float* window, int32_t win,
+                  const float* gout, const coma_tensor* dx, void* stream);
+
 /* ---- input pipeline (replaces VolumeDataset_ADNI_A4_combined.py:95-133,:62) ----
  * Nearest-neighbour resample of a raw fp32 (z, y, x) volume with voxel spacing sp_* (mm) onto a Do x Ho x Wo grid with
  * spacing nsp_* (same origin and axes, identity transform, ITK rounding), optional nan_to_num, optional zeroing where
