@@ -453,50 +453,8 @@ extern "C" int coma_l1_bwd(const coma_tensor* pred, const coma_tensor* gt, const
 }
 
 // ---- AdamW (torch.optim.AdamW: decoupled decay, bias-corrected, eps outside sqrt(v_hat)) ----
-__global__ __launch_bounds__(256) void adamw_k(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
-                                               float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                               const int32_t* step_dev, int vec4) {
-  if (step_dev) {   // step count lives on the device (hipGraph replays must not freeze it)
-    const float st = (float)*step_dev;
-    bc1 = 1.f - powf(b1, st);
-    bc2_sqrt = sqrtf(1.f - powf(b2, st));
-  }
-  auto upd = [&](float& pi, float gi, float& mi, float& vi) {
-    pi *= (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-  };
-  const int64_t n4 = vec4 ? n >> 2 : 0;        // 16 bytes per lane and stream where the four buffers are 16-byte aligned
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    upd(pv.x, gv.x, mv.x, vv.x); upd(pv.y, gv.y, mv.y, vv.y); upd(pv.z, gv.z, mv.z, vv.z); upd(pv.w, gv.w, mv.w, vv.w);
-    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    upd(pi, g[i], mi, vi);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-extern "C" int coma_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                          float eps, float weight_decay, int32_t step, const int32_t* step_dev, void* stream) {
-  COMA_CHECK(p && g && m && v && n >= 0 && (step >= 1 || step_dev), "adamw: bad argument");
-  if (n == 0) return 0;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2 = 1.f - powf(beta2, (float)step);
-  const int vec4 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-  hipLaunchKernelGGL(adamw_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, bc1, sqrtf(bc2), step_dev, vec4);
-  COMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- gradient accumulation and global-norm clipping beside adamw_k (optim.FusedAdamW(grad_acc_batch, max_grad_norm)) ----
-// Both kernels are deterministic: every double sum below runs in one fixed order (per thread over its own elements, the
-// xor tree of a wave, the four waves of a block in index order), no atomics.
+// adamw_k, adamw_ex_k and adamw_ema_k are three instantiations of adamw_body below: the plain step, the step on g * s
+// (gradient accumulation and clipping) and that step with the weight average moved in the same sweep.
 enum { ACC_BLOCKS = 1024 };      // grid cap of grad_accum_k == the longest table of partials
 
 __device__ __forceinline__ double ew_wave_sum(double v) {
@@ -510,6 +468,110 @@ __device__ __forceinline__ double ew_block_sum(double v, double* sh) {
   __syncthreads();
   return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
+
+struct AdamwArgs {                               // (the entry points fill it in this order; what a variant lacks stays zero)
+  float *p; const float* g; float *m, *v, *e;    // e: the average (EMA)
+  int64_t n;
+  float lr, b1, b2, eps, wd, bc1, bc2_sqrt;      // bc1, bc2_sqrt: adamw_launch
+  int step; const int32_t* step_dev;             // step count lives on the device when step_dev (hipGraph replays must not freeze it)
+  const int32_t* count_dev; const double* partials; int n_partials; const double* extra_sumsq; float max_norm; float* norm_out;  // WINDOW
+  float ema_decay; int ema_warmup;               // EMA
+  int vec4;                                      // adamw_launch: every buffer the variant touches is 16-byte aligned -> 16 bytes per lane and stream
+};
+
+// WINDOW: the update runs on g * s, s = clip coefficient / micro-batches in the window (see coma_adamw_ex in coma_unet.h);
+// every block forms s from the same table in the same order, so all blocks hold the bitwise-same value.  Without it the
+// gradient is taken as it is: no multiplication, no LDS.
+// EMA: then e += (1 - d_t)(p' - e) on the parameter just computed, while it is still in registers: 8 more bytes per element
+// instead of a 12-byte pass of its own.  d_t is formed here, in fp32, from the same device step count the bias corrections
+// read, so a replayed graph moves through the warm-up.  Without it e is neither loaded nor stored.
+template <bool WINDOW, bool EMA>
+__device__ __forceinline__ void adamw_body(const AdamwArgs a) {
+  float* const p = a.p; const float* const g = a.g; float* const m = a.m; float* const v = a.v; float* const e = a.e;
+  const int64_t n = a.n;
+  const float lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
+  float bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt, st = (float)a.step;
+  if (a.step_dev) {
+    st = (float)*a.step_dev;
+    bc1 = 1.f - powf(b1, st);
+    bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  }
+  float s = 1.f;
+  if constexpr (WINDOW) {
+    __shared__ double sh[4];
+    const double count = a.count_dev ? (double)*a.count_dev : 1.0;
+    double c = 1.0;
+    if (a.partials) {                               // (kernel argument: the whole block takes the branch)
+      double t = 0.0;
+      for (int k = threadIdx.x; k < a.n_partials; k += 256) t += a.partials[k];
+      t = ew_block_sum(t, sh);
+      if (a.extra_sumsq) t += *a.extra_sumsq;
+      const double norm = sqrt(t) / count;          // of the MEAN gradient: what clip_grad_norm_ returns
+      const double x = (double)a.max_norm / (norm + 1e-6);
+      c = x > 1.0 ? 1.0 : x;                        // (a NaN stays one: error_if_nonfinite=False)
+      if (a.norm_out && blockIdx.x == 0 && threadIdx.x == 0) *a.norm_out = (float)norm;
+    }
+    s = (float)(c / count);
+  }
+  float w = 0.f;
+  if constexpr (EMA) {
+    const float ema_decay = a.ema_decay;
+    const float d = a.ema_warmup ? fminf(ema_decay, (1.f + st) / (10.f + st)) : ema_decay;
+    w = 1.f - d;
+  }
+  auto upd = [&](float& pi, float gr, float& mi, float& vi, float& ei) {
+    float gi = gr;
+    if constexpr (WINDOW) gi = gr * s;
+    pi *= (1.f - lr * wd);
+    mi = b1 * mi + (1.f - b1) * gi;
+    vi = b2 * vi + (1.f - b2) * gi * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi -= (lr / bc1) * (mi / denom);
+    if constexpr (EMA) ei = fmaf(w, pi - ei, ei);
+  };
+  const int64_t n4 = a.vec4 ? n >> 2 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (EMA) ev = reinterpret_cast<float4*>(e)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    upd(pv.x, gv.x, mv.x, vv.x, ev.x); upd(pv.y, gv.y, mv.y, vv.y, ev.y);
+    upd(pv.z, gv.z, mv.z, vv.z, ev.z); upd(pv.w, gv.w, mv.w, vv.w, ev.w);
+    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
+    if constexpr (EMA) reinterpret_cast<float4*>(e)[i] = ev;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float pi = p[i], mi = m[i], vi = v[i], ei = 0.f;
+    if constexpr (EMA) ei = e[i];
+    upd(pi, g[i], mi, vi, ei);
+    p[i] = pi; m[i] = mi; v[i] = vi;
+    if constexpr (EMA) e[i] = ei;
+  }
+}
+__global__ __launch_bounds__(256) void adamw_k(const AdamwArgs a) { adamw_body<false, false>(a); }
+__global__ __launch_bounds__(256) void adamw_ex_k(const AdamwArgs a) { adamw_body<true, false>(a); }
+__global__ __launch_bounds__(256) void adamw_ema_k(const AdamwArgs a) { adamw_body<true, true>(a); }
+
+// what the three entry points share: the host-side bias corrections, the alignment test over the buffers the variant touches
+// (a.e is null without the average) and the launch
+static int adamw_launch(void (*kernel)(const AdamwArgs), AdamwArgs a, void* stream) {
+  if (a.n == 0) return 0;
+  a.bc1 = 1.f - powf(a.b1, (float)a.step);
+  a.bc2_sqrt = sqrtf(1.f - powf(a.b2, (float)a.step));
+  a.vec4 = ((((uintptr_t)a.p) | ((uintptr_t)a.g) | ((uintptr_t)a.m) | ((uintptr_t)a.v) | ((uintptr_t)a.e)) & 15) == 0;
+  hipLaunchKernelGGL(kernel, dim3(ew_grid(a.vec4 ? (a.n + 3) / 4 : a.n)), dim3(256), 0, (hipStream_t)stream, a);
+  COMA_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int coma_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int32_t step, const int32_t* step_dev, void* stream) {
+  COMA_CHECK(p && g && m && v && n >= 0 && (step >= 1 || step_dev), "adamw: bad argument");
+  return adamw_launch(adamw_k, {p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, step, step_dev}, stream);
+}
+
+// ---- gradient accumulation and global-norm clipping beside adamw_k (optim.FusedAdamW(grad_acc_batch, max_grad_norm)) ----
+// Both kernels are deterministic: every double sum below runs in one fixed order (per thread over its own elements, the
+// xor tree of a wave, the four waves of a block in index order), no atomics.
 
 // MODE 0: acc = g; 1: acc += g; 2: read g only.  -> this thread's sum of squares (fp64) of the values it handled.
 template <int MODE, bool NORM>
@@ -586,53 +648,7 @@ extern "C" int coma_grad_accum(float* acc, const float* g, int64_t n, const int3
   return 0;
 }
 
-// adamw_k on g * s, s = clip coefficient / micro-batches in the window (see coma_adamw_ex in coma_unet.h).  Every block
-// forms s from the same table in the same order, so all blocks hold the bitwise-same value.
-__global__ __launch_bounds__(256) void adamw_ex_k(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1,
-                                                  float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                  const int32_t* step_dev, const int32_t* count_dev, const double* partials,
-                                                  int n_partials, const double* extra_sumsq, float max_norm, float* norm_out,
-                                                  int vec4) {
-  __shared__ double sh[4];
-  if (step_dev) {
-    const float st = (float)*step_dev;
-    bc1 = 1.f - powf(b1, st);
-    bc2_sqrt = sqrtf(1.f - powf(b2, st));
-  }
-  const double count = count_dev ? (double)*count_dev : 1.0;
-  double c = 1.0;
-  if (partials) {                                   // (kernel argument: the whole block takes the branch)
-    double t = 0.0;
-    for (int k = threadIdx.x; k < n_partials; k += 256) t += partials[k];
-    t = ew_block_sum(t, sh);
-    if (extra_sumsq) t += *extra_sumsq;
-    const double norm = sqrt(t) / count;            // of the MEAN gradient: what clip_grad_norm_ returns
-    const double x = (double)max_norm / (norm + 1e-6);
-    c = x > 1.0 ? 1.0 : x;                          // (a NaN stays one: error_if_nonfinite=False)
-    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
-  }
-  const float s = (float)(c / count);
-  auto upd = [&](float& pi, float gr, float& mi, float& vi) {
-    const float gi = gr * s;
-    pi *= (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-  };
-  const int64_t n4 = vec4 ? n >> 2 : 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    upd(pv.x, gv.x, mv.x, vv.x); upd(pv.y, gv.y, mv.y, vv.y); upd(pv.z, gv.z, mv.z, vv.z); upd(pv.w, gv.w, mv.w, vv.w);
-    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    upd(pi, g[i], mi, vi);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
+// adamw_ex_k = adamw_body<WINDOW>: with no counter and no partials s is 1.0f and p, m, v are bitwise adamw_k's
 extern "C" int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                              float eps, float weight_decay, int32_t step, const int32_t* step_dev, const int32_t* count_dev,
                              const double* partials, int32_t n_partials, const double* extra_sumsq, float max_norm,
@@ -640,74 +656,12 @@ extern "C" int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64
   COMA_CHECK(p && g && m && v && n >= 0 && (step >= 1 || step_dev), "adamw_ex: bad argument");
   COMA_CHECK(!partials || (n_partials >= 0 && n_partials <= ACC_BLOCKS && max_norm >= 0.f),
              "adamw_ex: %d partials (at most %d), max_norm %g", n_partials, (int)ACC_BLOCKS, (double)max_norm);
-  if (n == 0) return 0;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2 = 1.f - powf(beta2, (float)step);
-  const int vec4 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0;
-  hipLaunchKernelGGL(adamw_ex_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, bc1, sqrtf(bc2), step_dev, count_dev, partials, (int)n_partials, extra_sumsq,
-                     max_norm, norm_out, vec4);
-  COMA_LAUNCH_CHECK();
-  return 0;
+  return adamw_launch(adamw_ex_k, {p, g, m, v, nullptr, n, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, step, step_dev, count_dev,
+                                   partials, n_partials, extra_sumsq, max_norm, norm_out}, stream);
 }
 
 // ---- weight EMA inside the AdamW sweep (optim.FusedAdamW(ema_decay, ema_warmup)) ----
-// adamw_ex_k's update of p, m, v, statement for statement (with no counter and no partials s is 1.0f and the three are
-// bitwise adamw_k's), then e += (1 - d_t)(p' - e) on the parameter just computed, while it is still in registers: 8 more
-// bytes per element instead of a 12-byte pass of its own.  d_t is formed here, in fp32, from the same device step count
-// the bias corrections read, so a replayed graph moves through the warm-up.
-__global__ __launch_bounds__(256) void adamw_ema_k(float* p, const float* g, float* m, float* v, float* e, int64_t n, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                   int step, const int32_t* step_dev, const int32_t* count_dev,
-                                                   const double* partials, int n_partials, const double* extra_sumsq,
-                                                   float max_norm, float* norm_out, float ema_decay, int ema_warmup, int vec4) {
-  __shared__ double sh[4];
-  float st = (float)step;
-  if (step_dev) {
-    st = (float)*step_dev;
-    bc1 = 1.f - powf(b1, st);
-    bc2_sqrt = sqrtf(1.f - powf(b2, st));
-  }
-  const double count = count_dev ? (double)*count_dev : 1.0;
-  double c = 1.0;
-  if (partials) {                                   // (kernel argument: the whole block takes the branch)
-    double t = 0.0;
-    for (int k = threadIdx.x; k < n_partials; k += 256) t += partials[k];
-    t = ew_block_sum(t, sh);
-    if (extra_sumsq) t += *extra_sumsq;
-    const double norm = sqrt(t) / count;
-    const double x = (double)max_norm / (norm + 1e-6);
-    c = x > 1.0 ? 1.0 : x;
-    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = (float)norm;
-  }
-  const float s = (float)(c / count);
-  const float d = ema_warmup ? fminf(ema_decay, (1.f + st) / (10.f + st)) : ema_decay;
-  const float w = 1.f - d;
-  auto upd = [&](float& pi, float gr, float& mi, float& vi, float& ei) {
-    const float gi = gr * s;
-    pi *= (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
-    ei = fmaf(w, pi - ei, ei);
-  };
-  const int64_t n4 = vec4 ? n >> 2 : 0;        // 16 bytes per lane and stream where the five buffers are 16-byte aligned
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-    float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-    float4 ev = reinterpret_cast<float4*>(e)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    upd(pv.x, gv.x, mv.x, vv.x, ev.x); upd(pv.y, gv.y, mv.y, vv.y, ev.y);
-    upd(pv.z, gv.z, mv.z, vv.z, ev.z); upd(pv.w, gv.w, mv.w, vv.w, ev.w);
-    reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(e)[i] = ev;
-  }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i], ei = e[i];
-    upd(pi, g[i], mi, vi, ei);
-    p[i] = pi; m[i] = mi; v[i] = vi; e[i] = ei;
-  }
-}
+// adamw_ema_k = adamw_body<WINDOW, EMA>: p, m, v are adamw_ex_k's by construction
 extern "C" int coma_adamw_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                               float eps, float weight_decay, int32_t step, const int32_t* step_dev, const int32_t* count_dev,
                               const double* partials, int32_t n_partials, const double* extra_sumsq, float max_norm,
@@ -716,16 +670,9 @@ extern "C" int coma_adamw_ema(float* p, const float* g, float* m, float* v, int6
   COMA_CHECK(!partials || (n_partials >= 0 && n_partials <= ACC_BLOCKS && max_norm >= 0.f),
              "adamw_ema: %d partials (at most %d), max_norm %g", n_partials, (int)ACC_BLOCKS, (double)max_norm);
   COMA_CHECK(ema_decay > 0.f && ema_decay < 1.f, "adamw_ema: ema_decay %g is not inside (0, 1)", (double)ema_decay);
-  if (n == 0) return 0;
-  COMA_CHECK(p && g && m && v && ema, "adamw_ema: null argument");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2 = 1.f - powf(beta2, (float)step);
-  const int vec4 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)ema)) & 15) == 0;
-  hipLaunchKernelGGL(adamw_ema_k, dim3(ew_grid(vec4 ? (n + 3) / 4 : n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr,
-                     beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), (int)step, step_dev, count_dev, partials, (int)n_partials,
-                     extra_sumsq, max_norm, norm_out, ema_decay, (int)ema_warmup, vec4);
-  COMA_LAUNCH_CHECK();
-  return 0;
+  COMA_CHECK(n == 0 || (p && g && m && v && ema), "adamw_ema: null argument");      // (n == 0: the pointers are not looked at)
+  return adamw_launch(adamw_ema_k, {p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, step, step_dev, count_dev,
+                                    partials, n_partials, extra_sumsq, max_norm, norm_out, ema_decay, ema_warmup}, stream);
 }
 
 // a <-> b by content: the parameters and their average change places while every address a captured graph or a parameter

@@ -184,8 +184,8 @@ class FusedAdamW(torch.optim.Optimizer):
         (they live, up to date, on the ranks that own them).  A step may also be taken slice by slice as the slices'
         gradients arrive (GradReducer.reduce_flat_and_step): advance=True on the first call only (the step count moves
         once), loose=True on one call only (parameters outside the flat buffer)."""
-        ema, ema_warm = self._ema_opts()
-        if ema is not None and self.shard_exchange is not None:
+        averaging = self.averaging
+        if averaging and self.shard_exchange is not None:
             raise ValueError(NO_EMA_SHARDED)
         if self._ema_in:
             raise RuntimeError(EMA_IN.format("step()"))
@@ -195,8 +195,6 @@ class FusedAdamW(torch.optim.Optimizer):
             ops.SidePrep.join()
             return self._micro_step()
         ops.SidePrep.join()       # the side stream's expert-gradient scatters land in the flat gradient buffer
-        g = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
         if not self.built:
             self._build()
         self._ensure_ema()
@@ -205,35 +203,45 @@ class FusedAdamW(torch.optim.Optimizer):
             self._step_dev += 1            # device-side copy: a captured step keeps counting under graph replay
             self._sparse_zero_bookkeeping()
         for off, k in ([(0, self.flat_p.numel())] if shards is None else shards):
-            if k > 0 and ema is not None:      # (elementwise: the average moves slice by slice with the parameters)
-                ops.adamw_ema_(self.flat_p[off:off + k], self.flat_g[off:off + k], self.flat_m[off:off + k],
-                               self.flat_v[off:off + k], self.flat_ema[off:off + k], ema, ema_warm, lr, b1, b2, eps, wd,
-                               self._flat_step, self._step_dev)
-            elif k > 0:
-                ops.adamw_(self.flat_p[off:off + k], self.flat_g[off:off + k], self.flat_m[off:off + k], self.flat_v[off:off + k],
-                           lr, b1, b2, eps, wd, self._flat_step, self._step_dev)
+            if k > 0:                      # (elementwise: the average moves slice by slice with the parameters)
+                sl = slice(off, off + k)
+                self._update(self.flat_p[sl], self.flat_g[sl], self.flat_m[sl], self.flat_v[sl],
+                             self.flat_ema[sl] if averaging else None, self._flat_step, self._step_dev)
         if not loose:
             return
         # backward is over: every slice of the step's zeroed arena is dead -- ONE memset clears them.  Behind the AdamW launch,
         # not in front of it: with ~170 MB of freshly dirtied lines ahead of it the 2.7 GB AdamW sweep measured 1.10 ms
         # instead of 0.85 ms.
         ops.ZeroArena.end_step()
-        for p in g["params"]:
+        for p in self.param_groups[0]["params"]:
             if id(p) in self._flat_ids or p.grad is None:
                 continue
-            st = self.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
-                st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
-            st["step"] += 1
-            gr = p.grad.float().contiguous()
-            if ema is not None:
-                ops.adamw_ema_(p.data.view(-1), gr.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
-                               self._loose_average(p), ema, ema_warm, lr, b1, b2, eps, wd, st["step"])
-                continue
-            ops.adamw_(p.data.view(-1), gr.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps,
-                       wd, st["step"])
+            st = self._loose_state(p)
+            self._update(p.data.view(-1), p.grad.float().contiguous().view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
+                         self._loose_average(p) if averaging else None, st["step"])
+
+    def _update(self, p, g, m, v, average, step, step_dev=None, window=None):
+        """One update of the flat fp32 (p, g, m, v) and, where there is one, of `average`, at update count `step` / the device
+        int32 `step_dev`.  window: ops.adamw_ex_'s (count_dev, partials, n_partials, extra_sumsq, max_norm, norm_out), or None
+        outside an accumulation window.  The one place that picks the kernel; the default step stays on coma_adamw."""
+        grp = self.param_groups[0]
+        hp = (float(grp["lr"]), *grp["betas"], grp["eps"], grp["weight_decay"])
+        if average is not None:
+            ops.adamw_ema_(p, g, m, v, average, *self._ema_opts(), *hp, step, step_dev, *(window or ()))
+        elif window is not None:
+            ops.adamw_ex_(p, g, m, v, *hp, step, step_dev, *window)
+        else:
+            ops.adamw_(p, g, m, v, *hp, step, step_dev)
+
+    def _loose_state(self, p):
+        """The moments of a parameter outside the flat buffer, created at its first update, with the count of this one."""
+        st = self.state[p]
+        if not st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
+            st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
+        st["step"] += 1
+        return st
 
     # -- accumulation window and clipping ----------------------------------------------
     def _window_opts(self):
@@ -309,7 +317,6 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _apply(self, K, mx, nb):
         g = self.param_groups[0]
-        lr, (b1, b2), eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
         acc_mode = K > 1
         src = self.flat_acc if acc_mode else self.flat_g
         count_dev = self._acc_dev if acc_mode else None
@@ -328,28 +335,15 @@ class FusedAdamW(torch.optim.Optimizer):
                 extra = self._extra_dev
         self._flat_step += 1
         self._step_dev += 1                # once per applied update (torch's step count under the usual accumulation idiom)
-        ema, ema_warm = self._ema_opts()   # the average moves here, on the applying update, never on a micro-batch
-        if ema is not None:
-            ops.adamw_ema_(self.flat_p, src, self.flat_m, self.flat_v, self.flat_ema, ema, ema_warm, lr, b1, b2, eps, wd,
-                           self._flat_step, self._step_dev, count_dev, partials, n_part, extra, mx or 0.0, norm_out)
-        else:
-            ops.adamw_ex_(self.flat_p, src, self.flat_m, self.flat_v, lr, b1, b2, eps, wd, self._flat_step, self._step_dev,
-                          count_dev, partials, n_part, extra, mx or 0.0, norm_out)
+        averaging = self.averaging         # the average moves here, on the applying update, never on a micro-batch
+        window = (count_dev, partials, n_part, extra, mx or 0.0)
+        self._update(self.flat_p, src, self.flat_m, self.flat_v, self.flat_ema if averaging else None, self._flat_step,
+                     self._step_dev, window + (norm_out,))
         ops.ZeroArena.end_step()           # (behind the sweep, as in step_shards)
         for p, a in loose_src:
-            st = self.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32)
-                st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
-            st["step"] += 1
-            if ema is not None:
-                ops.adamw_ema_(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), self._loose_average(p),
-                               ema, ema_warm, lr, b1, b2, eps, wd, st["step"], None, count_dev, partials, n_part, extra,
-                               mx or 0.0, None)
-                continue
-            ops.adamw_ex_(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), lr, b1, b2, eps, wd,
-                          st["step"], None, count_dev, partials, n_part, extra, mx or 0.0, None)
+            st = self._loose_state(p)
+            self._update(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
+                         self._loose_average(p) if averaging else None, st["step"], None, window + (None,))
         if acc_mode:
             self._acc_dev.zero_()
             for _, a in loose_src:

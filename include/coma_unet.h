@@ -436,15 +436,17 @@ int coma_grad_accum(float* acc, const float* g, int64_t n, const int32_t* count_
  *   included (error_if_nonfinite=False: the coefficient becomes NaN).  Every block sums the partials in the same order, so
  *   all blocks use the bitwise-same s.  norm_out (device fp32, may be NULL): block 0 stores `norm`, the unclipped norm of
  *   the mean gradient.  Slots of `partials` at or beyond n_partials (<= 1024) are not read.  With count == 1 and c == 1
- *   the results are bitwise those of coma_adamw. ---- */
+ *   the results are bitwise those of coma_adamw: the kernels of coma_adamw, coma_adamw_ex and coma_adamw_ema are
+ *   instantiations of one update body (adamw_body in csrc/elementwise.hip), which differ in the factor s and in the
+ *   average alone. ---- */
 int coma_adamw_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
                   const int32_t* count_dev, const double* partials, int32_t n_partials,
                   const double* extra_sumsq, float max_norm, float* norm_out, void* stream);
 
 /* ---- exponential moving average of the weights inside the same sweep (FusedAdamW(ema_decay, ema_warmup)).
- * coma_adamw_ema: coma_adamw_ex with the same arguments (p, m, v come out bitwise the same; with count_dev == NULL and
- *   partials == NULL bitwise coma_adamw's), then, per element, on the parameter p' just computed
+ * coma_adamw_ema: coma_adamw_ex with the same arguments (the same update body: p, m, v come out bitwise the same; with
+ *   count_dev == NULL and partials == NULL bitwise coma_adamw's), then, per element, on the parameter p' just computed
  *       e' = fmaf(1 - d_t, p' - e, e)                      (torch's get_ema_multi_avg_fn: lerp(e, p', 1 - d))
  *   stored to ema (length n, fp32).  d_t is formed in fp32 on the device:
  *       ema_warmup == 0:  d_t = ema_decay

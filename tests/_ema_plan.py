@@ -2,7 +2,8 @@
 FusedAdamW(ema_decay, ema_warmup) -- the decay d_t and e' = e + (1 - d_t)(p' - e) -- with the error bound of the kernel's
 fp32 arithmetic carried alongside, and the sizes at which the kernels are run.
 
-The bound counts roundings from the kernel source (csrc/elementwise.hip: adamw_ema_k), u = 2^-24:
+The bound counts roundings from the kernel source (csrc/elementwise.hip: adamw_body<WINDOW, EMA>, the body of adamw_ema_k),
+u = 2^-24:
   d_t ........................... ema_decay as passed (a float), or fminf(ema_decay, (1.f + t) / (10.f + t)): both sums are
                                   exact (small integers), the division rounds once: u d absolute; fminf is exact
   w = 1.f - d_t ................. one rounding: u w;  together |w^ - w| <= u (d + w)(1 + u) = u (1 + u)

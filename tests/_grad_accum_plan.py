@@ -2,7 +2,8 @@
 of one accumulation window of FusedAdamW(grad_acc_batch, max_grad_norm) -- accumulate, mean, global norm, clip coefficient,
 then _nonconv_plan.adamw_step -- with the error bounds of the kernels' arithmetic carried alongside the values.
 
-The bounds count roundings from the kernel sources (csrc/elementwise.hip: grad_accum_k, adamw_ex_k), u = 2^-24:
+The bounds count roundings from the kernel sources (csrc/elementwise.hip: grad_accum_k; adamw_body<WINDOW>, the body of
+adamw_ex_k), u = 2^-24:
   acc = g ......................... exact
   acc += g ........................ one rounding of the new value: u |acc|
   sum of squares .................. squares and sums in fp64: (n + 2) 2^-53 relative, on top of what acc's error moves it

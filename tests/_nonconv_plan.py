@@ -195,7 +195,7 @@ def adamw_bias_terms(b1, b2, t, pow_ulps=2.0):
 def adamw_step(st, g, t, hp=ADAMW_HP):
     """One AdamW step (torch.optim.AdamW: decoupled decay, bias-corrected, eps outside sqrt(v_hat)) in fp64 with the
     float32-rounded hyper-parameters, in place on `st`; the bounds bp / bm / bv follow the recurrence of the errors of
-    adamw_k's fp32 arithmetic (u = 2^-24 per rounding, counted from the source):
+    adamw_k's fp32 arithmetic (u = 2^-24 per rounding, counted from the source: adamw_body in csrc/elementwise.hip):
       m = b1 m + (1 - b1) g ............ 4 roundings over the mass b1 |m| + (1 - b1) |g|, the old error shrinks by b1
       v = b2 v + (1 - b2) g g .......... 5 roundings, all terms positive
       denom = sqrtf(v) / bc2s + eps .... sqrtf, division, sum: 3 roundings, + half of v's relative error, + eps(bc2s)
