@@ -10,6 +10,14 @@ from .inference import Predictor, fold_gate
 from .optim import FusedAdamW
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
+def __getattr__(name):
+    # Augment3D is exported, but its module is only imported by whoever asks for it: a run without augmentation loads nothing new
+    if name == "Augment3D":
+        from .augment import Augment3D
+        return Augment3D
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 DEFAULT_MODEL_PARAMS = (3, 1, 1, [32, 64, 128, 256, 512], [2] * 5)   # validation.py:727
 
 

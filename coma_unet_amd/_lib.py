@@ -109,6 +109,7 @@ SIGNATURES = {
     "coma_ssim_bwd": (_i32, [_TP, _TP, _vp, _vp, _i32, _vp, _TP, _vp]),
     "coma_resample_nearest": (_i32, [_vp, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _i32, _i32, _i32,
                               C.c_double, C.c_double, C.c_double, _f32, _i32, _vp, _vp]),
+    "coma_augment_warp": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp]),
     "coma_comm_unique_id": (_i32, [_vp]),
     "coma_comm_init": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_void_p)]),
     "coma_comm_destroy": (_i32, [_vp]),

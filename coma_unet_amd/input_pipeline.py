@@ -119,12 +119,14 @@ class Prefetcher:
     """Wraps an iterable of host samples {'mri','tau','roi': (Z,Y,X) float32 numpy arrays, 'spacing': (sx,sy,sz), optional
     other keys passed through} and yields device samples {'mri','tau','roi': (1,D,H,W) fp32 on `device`, ...}: the next
     sample's host->device copies (pinned staging buffers) and its resample kernels run on a side stream while the caller
-    trains on the current one."""
+    trains on the current one.  ``augment`` (an augment.Augment3D, default None: nothing changes): each prepared sample is
+    warped on the same side stream, one fused kernel behind ``prepare_sample``."""
 
-    def __init__(self, samples, device="cuda", new_spacing=NEW_SPACING, resize=True):
+    def __init__(self, samples, device="cuda", new_spacing=NEW_SPACING, resize=True, augment=None):
         self.it = iter(samples)
         self.device = torch.device(device)
         self.new_spacing, self.resize = new_spacing, resize
+        self.augment = augment
         self.stream = torch.cuda.Stream(device=self.device)
         self._pinned = {}
         self._next = None
@@ -150,6 +152,8 @@ class Prefetcher:
             vols = {k: self._to_device(k, s[k]) for k in ("mri", "tau", "roi")}
             dv = tuple(float(SITK_PIXEL_ID.get(np.dtype(s.get("stored_dtype", np.float32)), 8)) for _ in range(3))
             mri, tau, roi = prepare_sample(vols["mri"], vols["tau"], vols["roi"], s["spacing"], self.new_spacing, dv, self.resize)
+            if self.augment is not None:
+                mri, tau, roi = self.augment(mri.contiguous(), tau.contiguous(), roi.contiguous())
             out = {k: v for k, v in s.items() if k not in ("mri", "tau", "roi")}
             out.update(mri=mri, tau=tau, roi=roi)
         self._next = out

@@ -131,11 +131,19 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
      * ``ssim_weight`` / ``ssim_kwargs`` (None): with a weight, ``criterion.gen_loss`` is wrapped once in
        ``criterions.WithSSIM(gen_loss, ssim_weight, **ssim_kwargs)`` -- every sample's generative loss gains
        ``ssim_weight * (1 - SSIM_b)``, computed and differentiated by the fused SSIM kernels; the ROI tables and weight
-       updates stay the wrapped loss's.  With None the criterion is not touched and no SSIM kernel runs."""
+       updates stay the wrapped loss's.  With None the criterion is not touched and no SSIM kernel runs.
+     * ``augment`` (None | augment.Augment3D | dict of its arguments): on-device augmentation of every TRAINING batch -- one
+       fused kernel warps mri / tau / roi by the same random per-sample transform right after the batch reached the device,
+       before the graph load or the eager step (the augmented batch has the captured shapes, so the graph path is as
+       before); validation and ``contrastive_test`` never see it.  Under a ``reducer`` rank r draws from ``seed + r`` (a
+       dict's seed is offset here; pass an Augment3D built that way otherwise).  Checkpoints carry the generator state as
+       ``"augment_state"``; on resume restore it with ``checkpoint.load_checkpoint(..., augment=aug)`` or pass the file's
+       entry as ``augment_state=``.  With None nothing is imported, allocated or launched."""
     import torch.distributed as dist
     if "freeze_bn" in kwargs:
         model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
     with_ssim(criterion, kwargs.get("ssim_weight"), kwargs.get("ssim_kwargs"))
+    augment = kwargs.get("augment")
     cwd = os.getcwd()
     fold = kwargs.get("fold_id")
     base = f"{cwd}/training_folds/adni_a4_first_scan_combined_folds/tau_prediction_lookups"
@@ -154,6 +162,11 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     if reducer is not None and (grad_acc_batch != 1 or max_grad_norm is not None):
         raise ValueError(NO_EXCHANGE)
     world, rank = _dist_info(reducer)
+    if augment is not None:
+        from .augment import as_augmenter
+        augment = as_augmenter(augment, rank)
+        if kwargs.get("augment_state") is not None:
+            augment.load_state_dict(kwargs["augment_state"])
     if from_checkpoint:                                                                                   # :729-733
         optimizer = kwargs["optimizer"]
         start_epoch = kwargs["start_epoch"]
@@ -193,12 +206,12 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     with scope:
         return _train_epochs(model, criterion, train_loader, validation_loader, epochs, save_path, cuda_id, pred_sample_file,
                              kwargs, lookup, get_id, keep, device, optimizer, scheduler, reducer, world, rank, use_graph,
-                             start_epoch, val_iter, overfit_val_iter, checkpoint_iter)
+                             start_epoch, val_iter, overfit_val_iter, checkpoint_iter, augment)
 
 
 def _train_epochs(model, criterion, train_loader, validation_loader, epochs, save_path, cuda_id, pred_sample_file, kwargs, lookup,
                   get_id, keep, device, optimizer, scheduler, reducer, world, rank, use_graph, start_epoch, val_iter,
-                  overfit_val_iter, checkpoint_iter):
+                  overfit_val_iter, checkpoint_iter, augment=None):
     import torch.distributed as dist
     graphed, eager_done = None, 0
     epoch_avg_losses = []
@@ -221,6 +234,8 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
             priors = [lookup[get_id(p)] for p in tau_path]                                                # :809-810
             batch = dict(mri=_dev(mri, device), tau=_dev(tau, device), roi=_dev(roi, device), covars=_dev(covars, device),
                          roi_pred_dicts=priors)
+            if augment is not None:
+                batch["mri"], batch["tau"], batch["roi"] = augment(batch["mri"], batch["tau"], batch["roi"])
             if use_graph:
                 batch["roi_pred_dicts"] = model._priors(priors, batch["mri"].shape[0], device)            # (B, 36, 2) table
             if use_graph and graphed is None and eager_done >= 2 and optimizer.built:
@@ -263,7 +278,8 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
                          f"pos {epoch_pos / max(n_pos, 1):.6f}, neg {epoch_neg / max(n_neg, 1):.6f})")
         if save_path:                                                                                     # :943-955
             # every rank assembles the dict (FusedAdamW.state_dict() all-gathers sharded moments), rank 0 writes it
-            save_checkpoint(save_path, epoch, model, optimizer, loss, scheduler, checkpoint_iter=checkpoint_iter, write=rank == 0)
+            save_checkpoint(save_path, epoch, model, optimizer, loss, scheduler, checkpoint_iter=checkpoint_iter, write=rank == 0,
+                            augment=augment)
         if epoch % val_iter == 0 and validation_loader is not None and rank == 0:                         # :957-1017
             with torch.no_grad(), _eval_weights(optimizer, ema_eval, kwargs.get("predictor")):
                 val_save = os.path.join(save_path, f"{epoch}_output_samples") if save_path else ""

@@ -500,6 +500,25 @@ int coma_resample_nearest(const float* src, int32_t Dz, int32_t Hy, int32_t Wx, 
                           double nsp_y, double nsp_x, float default_value, int32_t nan_to_num,
                           const float* zero_where, void* stream);
 
+/* ---- on-device 3-D augmentation (build-side; DESIGN.md section 4 "Augmentation") ----
+ * One launch warps the MRI, tau and ROI-label volumes ((B, D, H, W) fp32, contiguous) of a batch by the same per-sample
+ * transform.  params[b] (device, COMA_AUG_NPARAM floats): a 3 x 4 row-major matrix A in (z, y, x) order mapping an
+ * output voxel index to a source voxel index, then mri_scale, mri_shift, mri_gamma, noise_sigma.  disp: optional
+ * (B, 3, gz, gy, gx) control grid of (z, y, x) displacements in voxels, 2..8 points per axis, interpolated trilinearly
+ * with the align-corners convention (NULL: none; gz, gy, gx are then ignored).  For output voxel o of sample b:
+ *   s = A_b (z, y, x, 1)^T + u_b(o);   roi_out = roi[floor(s + 0.5)] (0 outside);
+ *   tau_out = trilinear(tau, s), corners outside the volume contributing 0;
+ *   mri_out = mri_scale * g(trilinear(mri, s)) + mri_shift + noise_sigma * n, g(m) = m when mri_gamma == 1, else
+ *   max(m, 0)^mri_gamma; then mri_out = 0 where roi_out == 0.
+ * n = standard normal from Philox4x32-10 (key: low / high half of seed; counter: voxel index low, high, b, 0; index =
+ * (z H + y) W + x), Box-Muller on the top 24 bits of output words 0 and 1: u1 = ((w0 >> 8) + 1) 2^-24,
+ * u2 = (w1 >> 8) 2^-24, n = sqrt(-2 ln u1) cos(2 pi u2).  Not evaluated where noise_sigma == 0.
+ * Outputs must not overlap the inputs or each other (error status, nothing launched).                          */
+#define COMA_AUG_NPARAM 16
+int coma_augment_warp(const float* mri, const float* tau, const float* roi, float* mri_out, float* tau_out,
+                      float* roi_out, int32_t B, int32_t D, int32_t H, int32_t W, const float* params,
+                      const float* disp, int32_t gz, int32_t gy, int32_t gx, uint64_t seed, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (SURVEY.md section 8(b) last row, 8(e)): replaces the
  *      torch.nn.DataParallel the reference imports but never applies (attn_unet_data_parallel.py:32,1554).
  * One communicator per process (= per GPU).  Rank 0 creates the 128-byte id, the host distributes it by any means
