@@ -11,10 +11,14 @@ from .optim import FusedAdamW
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
 def __getattr__(name):
-    # Augment3D is exported, but its module is only imported by whoever asks for it: a run without augmentation loads nothing new
+    # Augment3D and GaussianSmooth3D are exported, but their modules are only imported by whoever asks for them: a run without
+    # augmentation or target smoothing loads nothing new
     if name == "Augment3D":
         from .augment import Augment3D
         return Augment3D
+    if name == "GaussianSmooth3D":
+        from .smooth import GaussianSmooth3D
+        return GaussianSmooth3D
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

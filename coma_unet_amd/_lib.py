@@ -110,6 +110,9 @@ SIGNATURES = {
     "coma_resample_nearest": (_i32, [_vp, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _vp, _i32, _i32, _i32,
                               C.c_double, C.c_double, C.c_double, _f32, _i32, _vp, _vp]),
     "coma_augment_warp": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp]),
+    "coma_gauss_smooth3d_tile": (None, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "coma_gauss_smooth3d": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32,
+                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _f32, _i32, _vp]),
     "coma_comm_unique_id": (_i32, [_vp]),
     "coma_comm_init": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_void_p)]),
     "coma_comm_destroy": (_i32, [_vp]),

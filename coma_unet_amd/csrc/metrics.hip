@@ -4,6 +4,7 @@
 // (attn_unet_data_parallel.py:1361-1397), the global MAE/MAPE/RSE/RRMSE reductions of contrastive_test
 // (:1214-1231) and RoiCorrMetric.acc_roi_corr's masked means (:49-60).  HBM-bound: 3 volume reads.
 #include "common.h"
+#include "resample.h"
 
 // stats[b][bin][k], k: 0 count, 1 sum|d|, 2 sum d^2, 3 sum g, 4 sum g^2, 5 sum p,
 //                      6 sum |d/g| over non-NaN entries, 7 count of non-NaN |d/g|
@@ -92,12 +93,6 @@ struct ResampleP {
   const float* zero_where;        // optional, dst-sized: output = 0 where this volume == 0
 };
 
-__device__ __forceinline__ int nn_index(int o, double ratio, int size) {
-  const double c = (double)o * ratio;                 // continuous input index
-  if (!(c >= -0.5 && c < (double)size - 0.5)) return -1;
-  return (int)floor(c + 0.5);                         // itk::Math::RoundHalfIntegerUp
-}
-
 __global__ __launch_bounds__(256) void resample_nn_k(ResampleP p) {
   const int64_t total = (int64_t)p.Do * p.Ho * p.Wo;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
@@ -105,11 +100,7 @@ __global__ __launch_bounds__(256) void resample_nn_k(ResampleP p) {
     const int ix = nn_index(x, p.rx, p.Wx), iy = nn_index(y, p.ry, p.Hy), iz = nn_index(z, p.rz, p.Dz);
     float v = p.default_value;
     if (ix >= 0 && iy >= 0 && iz >= 0) v = p.src[((int64_t)iz * p.Hy + iy) * p.Wx + ix];
-    if (p.nan_to_num) {                                // torch.nan_to_num defaults: nan -> 0, +-inf -> +-FLT_MAX
-      if (v != v) v = 0.f;
-      else if (v == INFINITY) v = 3.402823466e+38f;
-      else if (v == -INFINITY) v = -3.402823466e+38f;
-    }
+    if (p.nan_to_num) v = nan_to_num_f(v);
     if (p.zero_where && p.zero_where[e] == 0.f) v = 0.f;
     p.dst[e] = v;
   }

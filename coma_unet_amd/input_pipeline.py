@@ -53,16 +53,29 @@ def resample_nearest(vol: torch.Tensor, spacing_xyz, new_spacing=NEW_SPACING, de
     return out
 
 
-def prepare_sample(mri, tau, roi, spacing_xyz, new_spacing=NEW_SPACING, default_values=(8.0, 8.0, 8.0), resize=True):
+def prepare_sample(mri, tau, roi, spacing_xyz, new_spacing=NEW_SPACING, default_values=(8.0, 8.0, 8.0), resize=True, smoothing=None):
     """`__getitem__` of :58-66 for three raw (Z, Y, X) fp32 device volumes of one subject: returns
     (mri, tau, roi) as (1, D, H, W) fp32 tensors, the MRI zeroed where the (resampled) ROI mask is 0.
-    default_values: the SimpleITK pixel ids of the three files (float32 images: 8), see SITK_PIXEL_ID."""
+    default_values: the SimpleITK pixel ids of the three files (float32 images: 8), see SITK_PIXEL_ID.
+    smoothing (None | True | dict | smooth.GaussianSmooth3D; the reference's ``-smoothing``, VolumeDataset.py:138-140): the
+    tau target is Gaussian-smoothed after the resample and nan_to_num, as upstream; MRI and ROI are untouched.  With
+    ``resize`` that is ONE launch that stages the filter's halo through the resampler's index map (no resampled tau exists),
+    bit for bit what smoothing the resampled volume gives.  None: nothing is imported or launched."""
+    if smoothing is not None:
+        from .smooth import as_smoother
+        smoothing = as_smoother(smoothing)
     if not resize:
         roi_r = torch.nan_to_num(roi)
         mri_r = torch.nan_to_num(mri) * (roi_r != 0)
-        return mri_r.unsqueeze(0), torch.nan_to_num(tau).unsqueeze(0), roi_r.unsqueeze(0)
+        tau_r = torch.nan_to_num(tau)
+        if smoothing is not None:
+            tau_r = smoothing(tau_r.contiguous())
+        return mri_r.unsqueeze(0), tau_r.unsqueeze(0), roi_r.unsqueeze(0)
     roi_r = resample_nearest(roi, spacing_xyz, new_spacing, default_values[2])
-    tau_r = resample_nearest(tau, spacing_xyz, new_spacing, default_values[1])
+    if smoothing is not None:
+        tau_r = smoothing.resampled(tau, spacing_xyz, new_spacing, default_values[1])
+    else:
+        tau_r = resample_nearest(tau, spacing_xyz, new_spacing, default_values[1])
     mri_r = resample_nearest(mri, spacing_xyz, new_spacing, default_values[0], zero_where=roi_r)
     return mri_r.unsqueeze(0), tau_r.unsqueeze(0), roi_r.unsqueeze(0)
 
@@ -120,13 +133,20 @@ class Prefetcher:
     other keys passed through} and yields device samples {'mri','tau','roi': (1,D,H,W) fp32 on `device`, ...}: the next
     sample's host->device copies (pinned staging buffers) and its resample kernels run on a side stream while the caller
     trains on the current one.  ``augment`` (an augment.Augment3D, default None: nothing changes): each prepared sample is
-    warped on the same side stream, one fused kernel behind ``prepare_sample``."""
+    warped on the same side stream, one fused kernel behind ``prepare_sample``.  ``smoothing`` (None | True | dict | a
+    smooth.GaussianSmooth3D, default None: nothing changes): ``prepare_sample(smoothing=...)`` -- the tau target is smoothed on
+    the side stream, after the resample and in front of the augmentation warp, as upstream orders them.  Samples from such a
+    Prefetcher are already smoothed: do not also pass ``smooth_tau=`` to the loop that consumes them."""
 
-    def __init__(self, samples, device="cuda", new_spacing=NEW_SPACING, resize=True, augment=None):
+    def __init__(self, samples, device="cuda", new_spacing=NEW_SPACING, resize=True, augment=None, smoothing=None):
         self.it = iter(samples)
         self.device = torch.device(device)
         self.new_spacing, self.resize = new_spacing, resize
         self.augment = augment
+        if smoothing is not None:
+            from .smooth import as_smoother
+            smoothing = as_smoother(smoothing)
+        self.smoothing = smoothing
         self.stream = torch.cuda.Stream(device=self.device)
         self._pinned = {}
         self._next = None
@@ -151,7 +171,8 @@ class Prefetcher:
             # the pinned staging buffers are reused: the previous copies were waited for by the consumer's wait_stream
             vols = {k: self._to_device(k, s[k]) for k in ("mri", "tau", "roi")}
             dv = tuple(float(SITK_PIXEL_ID.get(np.dtype(s.get("stored_dtype", np.float32)), 8)) for _ in range(3))
-            mri, tau, roi = prepare_sample(vols["mri"], vols["tau"], vols["roi"], s["spacing"], self.new_spacing, dv, self.resize)
+            mri, tau, roi = prepare_sample(vols["mri"], vols["tau"], vols["roi"], s["spacing"], self.new_spacing, dv, self.resize,
+                                            self.smoothing)
             if self.augment is not None:
                 mri, tau, roi = self.augment(mri.contiguous(), tau.contiguous(), roi.contiguous())
             out = {k: v for k, v in s.items() if k not in ("mri", "tau", "roi")}

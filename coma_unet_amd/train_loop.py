@@ -72,6 +72,14 @@ def _dev(t, device):
     return t.to(device) if torch.is_tensor(t) else t
 
 
+def _smoother(spec):
+    """``smooth_tau=``: None stays None without importing anything; everything else goes through smooth.as_smoother."""
+    if spec is None:
+        return None
+    from .smooth import as_smoother
+    return as_smoother(spec)
+
+
 def _dist_info(reducer):
     """(world, rank) of the data-parallel job this loop is part of (1, 0 without a reducer / process group)."""
     import torch.distributed as dist
@@ -138,12 +146,20 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        before); validation and ``contrastive_test`` never see it.  Under a ``reducer`` rank r draws from ``seed + r`` (a
        dict's seed is offset here; pass an Augment3D built that way otherwise).  Checkpoints carry the generator state as
        ``"augment_state"``; on resume restore it with ``checkpoint.load_checkpoint(..., augment=aug)`` or pass the file's
-       entry as ``augment_state=``.  With None nothing is imported, allocated or launched."""
+       entry as ``augment_state=``.  With None nothing is imported, allocated or launched.
+     * ``smooth_tau`` (None | True | dict | smooth.GaussianSmooth3D): Gaussian smoothing of the tau target, the reference's
+       ``-smoothing`` flag -- ``batch["tau"]`` of EVERY training and EVERY validation batch is
+       filtered by one kernel launch right after it reached the device (the reference smooths both datasets), in training in
+       front of ``augment`` and of the graph load or the eager step; the captured graph and its addresses are untouched.
+       ``True`` is the reference's preset (sigma 1, in-plane).  ``contrastive_test`` receives the option through ``**kwargs``.
+       A loader fed by ``input_pipeline.Prefetcher(smoothing=...)`` already yields the smoothed target: the two are
+       alternatives, use one.  With None nothing is imported, allocated or launched."""
     import torch.distributed as dist
     if "freeze_bn" in kwargs:
         model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
     with_ssim(criterion, kwargs.get("ssim_weight"), kwargs.get("ssim_kwargs"))
     augment = kwargs.get("augment")
+    kwargs["smooth_tau"] = _smoother(kwargs.get("smooth_tau"))      # (built once; contrastive_test gets the instance)
     cwd = os.getcwd()
     fold = kwargs.get("fold_id")
     base = f"{cwd}/training_folds/adni_a4_first_scan_combined_folds/tau_prediction_lookups"
@@ -234,6 +250,8 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
             priors = [lookup[get_id(p)] for p in tau_path]                                                # :809-810
             batch = dict(mri=_dev(mri, device), tau=_dev(tau, device), roi=_dev(roi, device), covars=_dev(covars, device),
                          roi_pred_dicts=priors)
+            if kwargs["smooth_tau"] is not None:
+                batch["tau"] = kwargs["smooth_tau"](batch["tau"].contiguous())
             if augment is not None:
                 batch["mri"], batch["tau"], batch["roi"] = augment(batch["mri"], batch["tau"], batch["roi"])
             if use_graph:
@@ -419,7 +437,8 @@ def _save_corr_matrices(corr, save_path, prefix):
 
 def contrastive_test(model, test_loader, roi_indices, roi_weights, save_path="", cuda_id=0, pred_sample_file="",
                      with_train_loader=False, predictor=None, **kwargs):
-    """attn_unet_data_parallel.py:1129.  Returns (general, pos, neg) [+ embeddings when model.embeddings_out], each a
+    """attn_unet_data_parallel.py:1129.  ``smooth_tau=`` (build-side, see train_dp): the tau target of every batch is smoothed
+    on the device before anything reads it.  Returns (general, pos, neg) [+ embeddings when model.embeddings_out], each a
     tuple (mae, mape, rse, rrmse, ssim, roi_maes, roi_mapes, roi_rses, roi_wrrmses, roi_correlations); `general` carries an
     11th entry, the (never updated upstream, :1184-1185,1358) voxel-MAPE volume.
 
@@ -434,6 +453,7 @@ def contrastive_test(model, test_loader, roi_indices, roi_weights, save_path="",
     get_id = kwargs.get("extract_id", extract_id)
     device = torch.device("cuda", cuda_id) if isinstance(cuda_id, int) else torch.device(cuda_id)
     in_sample = bool(kwargs.get("in_sample_test", False))
+    smooth_tau = _smoother(kwargs.get("smooth_tau"))
     model.eval()
     model.set_training(False)                                                                             # :1144
     n_roi = len(roi_indices)
@@ -449,6 +469,8 @@ def contrastive_test(model, test_loader, roi_indices, roi_weights, save_path="",
             values = values[0]
         mri, tau, roi, abeta, covars, tau_path = _unpack(values)
         mri, tau, roi, covars = (_dev(t, device) for t in (mri, tau, roi, covars))
+        if smooth_tau is not None:
+            tau = smooth_tau(tau.contiguous())
         priors = [lookup[get_id(p)] for p in tau_path]
         if predictor is not None and predictor.fits(mri):
             # the folded, graph-replayed forward (inference.Predictor); its output buffer is rewritten by the next call

@@ -519,6 +519,38 @@ int coma_augment_warp(const float* mri, const float* tau, const float* roi, floa
                       float* roi_out, int32_t B, int32_t D, int32_t H, int32_t W, const float* params,
                       const float* disp, int32_t gz, int32_t gy, int32_t gx, uint64_t seed, void* stream);
 
+/* ---- Gaussian smoothing of the tau target (DESIGN.md section 4 "Target smoothing"; the reference's `-smoothing`) ----
+ * One launch filters a contiguous fp32 (B, D, H, W) batch of single-channel volumes into `out`, a distinct buffer, with a
+ * separable filter.  taps_z / taps_y / taps_x: host pointers to nz / ny / nx fp32 weights (copied into the launch, so a
+ * captured launch carries them); n must be odd, radius (n - 1) / 2 <= COMA_SMOOTH_MAX_RADIUS; a NULL pointer or n = 0
+ * skips that axis (no halo, no pass).  With radius r the output along an axis is  sum_k taps[k] v[i - r + k]  (a
+ * correlation), where v outside the volume is 0 (COMA_SMOOTH_ZEROS) or the nearest voxel inside (COMA_SMOOTH_NEAREST:
+ * the index is clamped, also where the volume is shorter than the radius).
+ * Arithmetic contract (tests compare bit for bit): the passes run in the order x, y, z over the axes that are not
+ * skipped; each pass computes s = 0, then s = fmaf(taps[k], v[i - r + k], s) for k = 0 .. n - 1 in fp32, and its
+ * result is rounded to fp32 before the next pass reads it.  With every axis skipped the output is a copy.
+ * Fused source: with `in` NULL and `src` the raw (B, Dz, Hy, Wx) volumes, the filter's input is what
+ * coma_resample_nearest(src, ..., default_value, nan_to_num, no zero_where) would write onto the (D, H, W) grid -- the
+ * same index map, the same values, so the result is bit for bit the two-step one -- without that volume existing.
+ * Exactly one of `in` and `src` is given; the other arguments of the unused form are ignored.
+ * A block owns a tile of outputs; coma_gauss_smooth3d_tile reports its extents for a launch whose largest radius is
+ * `radius` and whose z axis has a halo (z_filtered: nz > 1) or not.
+ * Error status, nothing launched: radius > COMA_SMOOTH_MAX_RADIUS, even n, B / D / H / W < 1, unknown boundary mode,
+ * `out` overlapping `in` or `src`, both or neither of `in` and `src`, non-positive spacings or source extents.        */
+#define COMA_SMOOTH_ZEROS 0
+#define COMA_SMOOTH_NEAREST 1
+#define COMA_SMOOTH_MAX_RADIUS 8
+#define COMA_SMOOTH_SMALL_RADIUS 4   /* up to here: the full tile and at least two blocks per CU */
+#define COMA_SMOOTH_TILE_Z 8         /* halved when radius > COMA_SMOOTH_SMALL_RADIUS and the z axis has a halo */
+#define COMA_SMOOTH_TILE_Y 8
+#define COMA_SMOOTH_TILE_X 32
+void coma_gauss_smooth3d_tile(int32_t radius, int32_t z_filtered, int32_t* tz, int32_t* ty, int32_t* tx);
+int coma_gauss_smooth3d(const float* in, float* out, int32_t B, int32_t D, int32_t H, int32_t W, const float* taps_z,
+                        int32_t nz, const float* taps_y, int32_t ny, const float* taps_x, int32_t nx,
+                        int32_t boundary, const float* src, int32_t Dz, int32_t Hy, int32_t Wx, double sp_z,
+                        double sp_y, double sp_x, double nsp_z, double nsp_y, double nsp_x, float default_value,
+                        int32_t nan_to_num, void* stream);
+
 /* ---- data-parallel gradient exchange over RCCL / xGMI (SURVEY.md section 8(b) last row, 8(e)): replaces the
  *      torch.nn.DataParallel the reference imports but never applies (attn_unet_data_parallel.py:32,1554).
  * One communicator per process (= per GPU).  Rank 0 creates the 128-byte id, the host distributes it by any means
