@@ -7,7 +7,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is absent)
 from .attn_unet_data_parallel import (ContrastiveAttentionUNET_DP, ObservableAttentionUnet, AttentionLayer,
                                       ObservableAttentionBlock, UpBlock, ProjectionHead, StackedFusionConvLayers)
 from .inference import Predictor, fold_gate
-from .optim import FusedAdamW
+from .optim import FusedAdamW, LRSchedule
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
 def __getattr__(name):

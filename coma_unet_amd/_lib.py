@@ -130,6 +130,9 @@ SIGNATURES = {
                              _vp, _vp]),
     "coma_adamw_ema": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp, _f32,
                               _vp, _vp, _f32, _i32, _vp]),
+    "coma_adamw_sched": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _i32, _vp, _f32,
+                                _vp, _vp, _f32, _i32, _i32, _i32, _f32, _i32, _f32, _i32, _f32, _i32, _vp, _f32, _vp, _vp, _vp,
+                                _i32, _i64, _vp, _vp]),
     "coma_swap_f32": (_i32, [_vp, _vp, _i64, _vp]),
 }
 

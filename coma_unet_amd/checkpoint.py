@@ -9,7 +9,8 @@ generator's position, ``augment.Augment3D.state_dict``) only when the run augmen
 
 ``model_state_dict`` carries the reference's key names (this build's module tree mirrors the MONAI / CondConv one),
 ``optimizer_state_dict`` is ``torch.optim.AdamW``-shaped (``FusedAdamW.state_dict``), so a file written here loads into
-the reference stack and vice versa.  Files are read with ``weights_only=True`` (nothing in them needs unpickling).
+the reference stack and vice versa; a learning-rate schedule and per-parameter options (``FusedAdamW(lr_schedule=...,
+param_options=...)``) travel in its ``param_groups`` as plain data, nothing here knows of them.  Files are read with ``weights_only=True`` (nothing in them needs unpickling).
 """
 from __future__ import annotations
 

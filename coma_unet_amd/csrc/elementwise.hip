@@ -479,17 +479,100 @@ struct AdamwArgs {                               // (the entry points fill it in
   int vec4;                                      // adamw_launch: every buffer the variant touches is 16-byte aligned -> 16 bytes per lane and stream
 };
 
+// SCHED (coma_adamw_sched): what the scheduled kernels take on top of AdamwArgs; the other kernels never see it
+enum { SCHED_CONSTANT = 0, SCHED_COSINE = 1, SCHED_LINEAR = 2, SCHED_STEP = 3, SCHED_KINDS = 4 };
+enum { MAX_SEGS = 2048 };        // longest segment table: 16 bytes of LDS per segment, 32 KB per block at the cap
+struct AdamwSched {
+  const float* lr_dev;                                     // the base rate
+  int kind, Wm; float f0; int T; float r; int S; float gamma;
+  int step; const int32_t* step_dev;                       // the global applied-update count the schedule is evaluated at (both zero: AdamwArgs')
+  float lr_scale;                                          // uniform scale (n_segs == 0)
+  const int64_t* seg_end; const float* seg_lr_scale; const float* seg_wd; int n_segs; int64_t elem_base;
+  float* lr_out;
+};
+extern __shared__ int64_t adamw_seg_lds[];                 // SCHED with a table: seg_end[n_segs] | lr_t * seg_lr_scale[n_segs] | seg_wd[n_segs]
+
+// The update of the SCHED kernels: adamw_body's `upd` operation by operation, with contraction switched off and every fused
+// multiply-add written out, because lr and wd vary from element to element there and the compiler's choice of what to fuse
+// must not.  It is the choice it makes for `upd` in adamw_k / adamw_ex_k / adamw_ema_k, which differs between their two loops:
+// the 16-byte loop fuses the moment updates (FUSED_MV), the scalar loop rounds product and sum separately; both fuse
+// 1 - lr * wd and the parameter update.  Keeping that per loop is what makes the scheduled kernels bitwise the unscheduled
+// ones on either path.
+template <bool WINDOW, bool EMA, bool FUSED_MV>
+__device__ __forceinline__ void adamw_upd_pinned(float& pi, float gr, float& mi, float& vi, float& ei, float lr, float wd, float b1,
+                                                 float b2, float eps, float bc1, float bc2_sqrt, float s, float w) {
+#pragma clang fp contract(off)
+  const float gi = WINDOW ? gr * s : gr;
+  const float a1 = (1.f - b1) * gi, a2 = ((1.f - b2) * gi) * gi;
+  if (FUSED_MV) {
+    mi = __builtin_fmaf(b1, mi, a1);
+    vi = __builtin_fmaf(b2, vi, a2);
+  } else {
+    mi = b1 * mi + a1;
+    vi = b2 * vi + a2;
+  }
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pi = __builtin_fmaf(__builtin_fmaf(-lr, wd, 1.f), pi, -((lr / bc1) * (mi / denom)));
+  if (EMA) ei = __builtin_fmaf(w, pi - ei, ei);
+}
+
 // WINDOW: the update runs on g * s, s = clip coefficient / micro-batches in the window (see coma_adamw_ex in coma_unet.h);
 // every block forms s from the same table in the same order, so all blocks hold the bitwise-same value.  Without it the
 // gradient is taken as it is: no multiplication, no LDS.
 // EMA: then e += (1 - d_t)(p' - e) on the parameter just computed, while it is still in registers: 8 more bytes per element
 // instead of a 12-byte pass of its own.  d_t is formed here, in fp32, from the same device step count the bias corrections
 // read, so a replayed graph moves through the warm-up.  Without it e is neither loaded nor stored.
-template <bool WINDOW, bool EMA>
-__device__ __forceinline__ void adamw_body(const AdamwArgs a) {
+// SCHED: the learning rate is lr_t = *lr_dev * warm(s) * decay(u), formed here in fp32 from a device update count (every
+// block evaluates the same expressions on the same inputs: one value), and an element takes lr_t * scale and the decay of
+// the segment of the flat buffer it lies in.  The table is staged in LDS once per block and searched there: a 16-byte chunk
+// costs one binary search (<= 11 LDS reads) and, where no boundary crosses it, nothing more.  Without it lr and wd are the
+// kernel arguments and no table, no LDS and no search exist.
+template <bool WINDOW, bool EMA, bool SCHED = false>
+__device__ __forceinline__ void adamw_body(const AdamwArgs a, const AdamwSched sc = AdamwSched{}) {
   float* const p = a.p; const float* const g = a.g; float* const m = a.m; float* const v = a.v; float* const e = a.e;
   const int64_t n = a.n;
-  const float lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
+  const float b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd;
+  float lr = a.lr;
+  int nseg = 0;
+  const int64_t* const seg_e = SCHED ? adamw_seg_lds : nullptr;
+  const float *seg_l = nullptr, *seg_w = nullptr;
+  if constexpr (SCHED) {
+    int t = sc.step_dev ? *sc.step_dev : sc.step;
+    if (!sc.step_dev && sc.step == 0) t = a.step_dev ? *a.step_dev : a.step;
+    const int s = t > 0 ? t - 1 : 0;                      // torch: scheduler.step() follows optimizer.step()
+    float warm = 1.f;
+    if (sc.Wm > 0) warm = sc.f0 + (1.f - sc.f0) * ((float)(s < sc.Wm ? s : sc.Wm) / (float)sc.Wm);
+    int u = s - sc.Wm;
+    if (u < 0) u = 0;
+    if (sc.kind != SCHED_STEP && u > sc.T) u = sc.T;
+    float decay = 1.f;
+    if (sc.kind == SCHED_COSINE) decay = sc.r + (1.f - sc.r) * (0.5f * (1.f + cosf(3.14159265358979f * ((float)u / (float)sc.T))));
+    else if (sc.kind == SCHED_LINEAR) decay = 1.f - (1.f - sc.r) * ((float)u / (float)sc.T);
+    else if (sc.kind == SCHED_STEP) decay = powf(sc.gamma, (float)(u / sc.S));
+    const float lr_t = (*sc.lr_dev * warm) * decay;
+    if (sc.lr_out && blockIdx.x == 0 && threadIdx.x == 0) *sc.lr_out = lr_t;
+    lr = lr_t * sc.lr_scale;
+    nseg = sc.n_segs;
+    if (nseg > 0) {                                       // (kernel argument: the whole block takes the branch)
+      int64_t* const le = adamw_seg_lds;
+      float* const ll = reinterpret_cast<float*>(le + nseg);
+      float* const lw = ll + nseg;
+      for (int k = threadIdx.x; k < nseg; k += 256) {
+        le[k] = sc.seg_end[k]; ll[k] = lr_t * sc.seg_lr_scale[k]; lw[k] = sc.seg_wd[k];
+      }
+      __syncthreads();
+      seg_l = ll; seg_w = lw;
+    }
+  }
+  // first segment whose end lies beyond flat coordinate c (the last one for a coordinate at or past the table's end)
+  auto seg_of = [&](int64_t c) {
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (seg_e[mid] > c) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+  };
   float bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt, st = (float)a.step;
   if (a.step_dev) {
     st = (float)*a.step_dev;
@@ -519,6 +602,8 @@ __device__ __forceinline__ void adamw_body(const AdamwArgs a) {
     const float d = a.ema_warmup ? fminf(ema_decay, (1.f + st) / (10.f + st)) : ema_decay;
     w = 1.f - d;
   }
+  // (the SCHED kernels do not go through this lambda but through adamw_upd_pinned, the same operations with the fusion pinned:
+  // an edit here must be mirrored there, and tests/test_lr_schedule_kernels_gpu.py holds the two together bit for bit)
   auto upd = [&](float& pi, float gr, float& mi, float& vi, float& ei) {
     float gi = gr;
     if constexpr (WINDOW) gi = gr * s;
@@ -535,15 +620,46 @@ __device__ __forceinline__ void adamw_body(const AdamwArgs a) {
     float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (EMA) ev = reinterpret_cast<float4*>(e)[i];
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    upd(pv.x, gv.x, mv.x, vv.x, ev.x); upd(pv.y, gv.y, mv.y, vv.y, ev.y);
-    upd(pv.z, gv.z, mv.z, vv.z, ev.z); upd(pv.w, gv.w, mv.w, vv.w, ev.w);
+    if constexpr (SCHED) {
+      float l0 = lr, l1 = lr, l2 = lr, l3 = lr, w0 = wd, w1 = wd, w2 = wd, w3 = wd;
+      if (nseg > 0) {
+        const int64_t c = sc.elem_base + 4 * i;
+        int k = seg_of(c);
+        l0 = seg_l[k]; w0 = seg_w[k];
+        if (k == nseg - 1 || seg_e[k] >= c + 4) {         // no boundary inside the chunk
+          l1 = l2 = l3 = l0; w1 = w2 = w3 = w0;
+        } else {                                          // segments may be shorter than the chunk: step element by element
+          while (k < nseg - 1 && seg_e[k] <= c + 1) ++k;
+          l1 = seg_l[k]; w1 = seg_w[k];
+          while (k < nseg - 1 && seg_e[k] <= c + 2) ++k;
+          l2 = seg_l[k]; w2 = seg_w[k];
+          while (k < nseg - 1 && seg_e[k] <= c + 3) ++k;
+          l3 = seg_l[k]; w3 = seg_w[k];
+        }
+      }
+#define U(c, l, wdc) adamw_upd_pinned<WINDOW, EMA, true>(pv.c, gv.c, mv.c, vv.c, ev.c, l, wdc, b1, b2, eps, bc1, bc2_sqrt, s, w)
+      U(x, l0, w0); U(y, l1, w1); U(z, l2, w2); U(w, l3, w3);
+#undef U
+    } else {
+      upd(pv.x, gv.x, mv.x, vv.x, ev.x); upd(pv.y, gv.y, mv.y, vv.y, ev.y);
+      upd(pv.z, gv.z, mv.z, vv.z, ev.z); upd(pv.w, gv.w, mv.w, vv.w, ev.w);
+    }
     reinterpret_cast<float4*>(p)[i] = pv; reinterpret_cast<float4*>(m)[i] = mv; reinterpret_cast<float4*>(v)[i] = vv;
     if constexpr (EMA) reinterpret_cast<float4*>(e)[i] = ev;
   }
   for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float pi = p[i], mi = m[i], vi = v[i], ei = 0.f;
     if constexpr (EMA) ei = e[i];
-    upd(pi, g[i], mi, vi, ei);
+    if constexpr (SCHED) {
+      float l0 = lr, w0 = wd;
+      if (nseg > 0) {
+        const int k = seg_of(sc.elem_base + i);
+        l0 = seg_l[k]; w0 = seg_w[k];
+      }
+      adamw_upd_pinned<WINDOW, EMA, false>(pi, g[i], mi, vi, ei, l0, w0, b1, b2, eps, bc1, bc2_sqrt, s, w);
+    } else {
+      upd(pi, g[i], mi, vi, ei);
+    }
     p[i] = pi; m[i] = mi; v[i] = vi;
     if constexpr (EMA) e[i] = ei;
   }
@@ -551,15 +667,22 @@ __device__ __forceinline__ void adamw_body(const AdamwArgs a) {
 __global__ __launch_bounds__(256) void adamw_k(const AdamwArgs a) { adamw_body<false, false>(a); }
 __global__ __launch_bounds__(256) void adamw_ex_k(const AdamwArgs a) { adamw_body<true, false>(a); }
 __global__ __launch_bounds__(256) void adamw_ema_k(const AdamwArgs a) { adamw_body<true, true>(a); }
+__global__ __launch_bounds__(256) void adamw_sched_k(const AdamwArgs a, const AdamwSched sc) { adamw_body<true, false, true>(a, sc); }
+__global__ __launch_bounds__(256) void adamw_sched_ema_k(const AdamwArgs a, const AdamwSched sc) { adamw_body<true, true, true>(a, sc); }
 
 // what the three entry points share: the host-side bias corrections, the alignment test over the buffers the variant touches
 // (a.e is null without the average) and the launch
-static int adamw_launch(void (*kernel)(const AdamwArgs), AdamwArgs a, void* stream) {
-  if (a.n == 0) return 0;
+// (coma_adamw_sched launches its two kernels itself -- a second argument, dynamic LDS -- behind the same adamw_prepare)
+static dim3 adamw_prepare(AdamwArgs& a) {
   a.bc1 = 1.f - powf(a.b1, (float)a.step);
   a.bc2_sqrt = sqrtf(1.f - powf(a.b2, (float)a.step));
   a.vec4 = ((((uintptr_t)a.p) | ((uintptr_t)a.g) | ((uintptr_t)a.m) | ((uintptr_t)a.v) | ((uintptr_t)a.e)) & 15) == 0;
-  hipLaunchKernelGGL(kernel, dim3(ew_grid(a.vec4 ? (a.n + 3) / 4 : a.n)), dim3(256), 0, (hipStream_t)stream, a);
+  return dim3(ew_grid(a.vec4 ? (a.n + 3) / 4 : a.n));
+}
+static int adamw_launch(void (*kernel)(const AdamwArgs), AdamwArgs a, void* stream) {
+  if (a.n == 0) return 0;
+  const dim3 grid = adamw_prepare(a);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   COMA_LAUNCH_CHECK();
   return 0;
 }
@@ -673,6 +796,46 @@ extern "C" int coma_adamw_ema(float* p, const float* g, float* m, float* v, int6
   COMA_CHECK(n == 0 || (p && g && m && v && ema), "adamw_ema: null argument");      // (n == 0: the pointers are not looked at)
   return adamw_launch(adamw_ema_k, {p, g, m, v, ema, n, lr, beta1, beta2, eps, weight_decay, 0.f, 0.f, step, step_dev, count_dev,
                                     partials, n_partials, extra_sumsq, max_norm, norm_out, ema_decay, ema_warmup}, stream);
+}
+
+// ---- learning-rate schedule and per-segment options inside the AdamW sweep (optim.FusedAdamW(lr_schedule, param_options)) ----
+// adamw_sched_k = adamw_body<WINDOW, false, SCHED>, adamw_sched_ema_k = adamw_body<WINDOW, EMA, SCHED>: with lr_scale 1 and no
+// table p, m, v (and e) are bitwise those of the unscheduled kernels called with lr = *lr_out
+extern "C" int coma_adamw_sched(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
+                                float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                                const int32_t* count_dev, const double* partials, int32_t n_partials, const double* extra_sumsq,
+                                float max_norm, float* norm_out, float* ema, float ema_decay, int32_t ema_warmup,
+                                int32_t sched_kind, int32_t warmup_steps, float warmup_start, int32_t total_steps, float min_ratio,
+                                int32_t step_size, float gamma, int32_t sched_step, const int32_t* sched_step_dev, float lr_scale,
+                                const int64_t* seg_end, const float* seg_lr_scale, const float* seg_wd, int32_t n_segs,
+                                int64_t elem_base, float* lr_out, void* stream) {
+  COMA_CHECK(n >= 0 && (step >= 1 || step_dev) && sched_step >= 0, "adamw_sched: bad argument");
+  COMA_CHECK(lr_dev, "adamw_sched: lr_dev is null (the base rate lives in device memory)");
+  COMA_CHECK(!partials || (n_partials >= 0 && n_partials <= ACC_BLOCKS && max_norm >= 0.f),
+             "adamw_sched: %d partials (at most %d), max_norm %g", n_partials, (int)ACC_BLOCKS, (double)max_norm);
+  COMA_CHECK(!ema || (ema_decay > 0.f && ema_decay < 1.f), "adamw_sched: ema_decay %g is not inside (0, 1)", (double)ema_decay);
+  COMA_CHECK(sched_kind >= 0 && sched_kind < SCHED_KINDS, "adamw_sched: unknown schedule kind %d", sched_kind);
+  COMA_CHECK((sched_kind != SCHED_COSINE && sched_kind != SCHED_LINEAR) || total_steps >= 1,
+             "adamw_sched: total_steps %d (the schedule needs T >= 1)", total_steps);
+  COMA_CHECK(step_size >= 1 && gamma > 0.f && gamma <= 1.f, "adamw_sched: step_size %d (>= 1), gamma %g (inside (0, 1])",
+             step_size, (double)gamma);
+  COMA_CHECK(min_ratio >= 0.f && min_ratio <= 1.f && warmup_start > 0.f && warmup_start <= 1.f && warmup_steps >= 0,
+             "adamw_sched: min_ratio %g (inside [0, 1]), warmup_start %g (inside (0, 1]), warmup_steps %d (>= 0)",
+             (double)min_ratio, (double)warmup_start, warmup_steps);
+  COMA_CHECK(n_segs >= 0 && n_segs <= MAX_SEGS, "adamw_sched: %d segments (at most %d)", n_segs, (int)MAX_SEGS);
+  COMA_CHECK(n_segs == 0 || (seg_end && seg_lr_scale && seg_wd && elem_base >= 0), "adamw_sched: segment table: null argument");
+  COMA_CHECK(n == 0 || (p && g && m && v), "adamw_sched: null argument");             // (n == 0: the pointers are not looked at)
+  if (n == 0) return 0;
+  AdamwArgs a = {p, g, m, v, ema, n, 0.f, beta1, beta2, eps, weight_decay, 0.f, 0.f, step, step_dev, count_dev,
+                 partials, n_partials, extra_sumsq, max_norm, norm_out, ema_decay, ema_warmup};
+  const AdamwSched sc = {lr_dev, sched_kind, warmup_steps, warmup_start, total_steps, min_ratio, step_size, gamma, sched_step,
+                         sched_step_dev, lr_scale, seg_end, seg_lr_scale, seg_wd, n_segs, elem_base, lr_out};
+  const dim3 grid = adamw_prepare(a);
+  const size_t lds = (size_t)n_segs * (sizeof(int64_t) + 2 * sizeof(float));
+  if (ema) hipLaunchKernelGGL(adamw_sched_ema_k, grid, dim3(256), lds, (hipStream_t)stream, a, sc);
+  else hipLaunchKernelGGL(adamw_sched_k, grid, dim3(256), lds, (hipStream_t)stream, a, sc);
+  COMA_LAUNCH_CHECK();
+  return 0;
 }
 
 // a <-> b by content: the parameters and their average change places while every address a captured graph or a parameter

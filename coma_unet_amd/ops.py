@@ -1573,6 +1573,36 @@ def adamw_ema_(p, g, m, v, ema, ema_decay, ema_warmup, lr, beta1, beta2, eps, wd
                              ema_decay, int(bool(ema_warmup)), L.stream()), "coma_adamw_ema")
 
 
+SCHED_KINDS = ("constant", "cosine", "linear", "step")      # coma_adamw_sched's sched_kind, by index
+MAX_SEGS = 2048                                             # its longest segment table
+
+
+def adamw_sched_(p, g, m, v, lr_dev, sched, beta1, beta2, eps, wd, step, step_dev=None, sched_step=0, sched_step_dev=None,
+                 lr_scale=1.0, segs=None, elem_base=0, lr_out=None, ema=None, ema_decay=0.0, ema_warmup=False, count_dev=None,
+                 partials=None, n_partials=0, extra_sumsq=None, max_norm=0.0, norm_out=None):
+    """adamw_ex_ (adamw_ema_ with `ema`) at the learning rate the kernel forms itself: lr_t = lr_dev[0] * warm * decay of the
+    schedule `sched` = (kind index, warmup_steps, warmup_start, total_steps, min_ratio, step_size, gamma) at the update count
+    `sched_step_dev` / `sched_step` (both unset: `step_dev` / `step`), written to the device fp32 `lr_out`.  segs: None -- every
+    element takes lr_t * lr_scale and wd -- or device tensors (seg_end int64, seg_lr_scale fp32, seg_wd fp32) of one length:
+    element i, at flat coordinate elem_base + i, takes the options of the first segment that ends beyond it."""
+    assert p.is_contiguous() and g.is_contiguous() and p.dtype == torch.float32 and g.dtype == torch.float32
+    assert ema is None or (ema.is_contiguous() and ema.dtype == torch.float32 and ema.numel() == p.numel())
+    assert lr_dev is None or lr_dev.dtype == torch.float32
+    seg_end = seg_scale = seg_wd = None
+    n_segs = 0
+    if segs is not None:
+        seg_end, seg_scale, seg_wd = segs
+        n_segs = seg_end.numel()
+        assert seg_end.dtype == torch.int64 and seg_scale.dtype == seg_wd.dtype == torch.float32
+        assert seg_scale.numel() == seg_wd.numel() == n_segs
+    kind, wm, f0, T, r, S, gamma = sched
+    check(lib.coma_adamw_sched(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(lr_dev), beta1, beta2, eps, wd, step, ptr(step_dev),
+                               ptr(count_dev), ptr(partials), n_partials, ptr(extra_sumsq), max_norm, ptr(norm_out), ptr(ema),
+                               ema_decay, int(bool(ema_warmup)), kind, wm, f0, T, r, S, gamma, sched_step, ptr(sched_step_dev),
+                               lr_scale, ptr(seg_end), ptr(seg_scale), ptr(seg_wd), n_segs, elem_base, ptr(lr_out), L.stream()),
+          "coma_adamw_sched")
+
+
 def swap_f32_(a, b):
     """Exchange the contents of two disjoint contiguous fp32 tensors in place (one launch)."""
     assert a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype == torch.float32 and a.numel() == b.numel()

@@ -18,8 +18,16 @@ attn_unet_data_parallel.py:887-890, do not divide -- the mean keeps ``lr`` compa
 ``swap_ema()`` / ``ema_weights()`` exchange parameters and average by content (``ops.swap_f32_``), so that every view and every
 captured graph keeps its address; ``ema_state_dict`` / ``load_ema_state_dict`` serialise it.  With the option off nothing of it
 exists.
+
+``lr_schedule`` / ``param_options``: the update's kernel forms its own learning rate -- a base rate held in device memory
+times warm-up and decay factors (``LRSchedule``) evaluated at the device update count -- and takes ``lr_scale`` /
+``weight_decay`` per parameter from a device table of segments of the flat buffer (``ops.adamw_sched_``).  A replayed graph
+walks through the schedule and a plateau scheduler's change of ``param_groups[0]["lr"]`` needs no new capture.  With both
+options off nothing of it exists and the launches are the ones above.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -51,6 +59,160 @@ def _check_ema_opts(ema_decay, ema_warmup):
         raise ValueError(f"ema_warmup must be a bool, got {ema_warmup!r}")
 
 
+class LRSchedule:
+    """Per-update learning-rate factor: linear warm-up (torch's ``LinearLR(start_factor=warmup_start,
+    total_iters=warmup_steps)``), then one of ``constant``, ``cosine`` (``CosineAnnealingLR``'s closed form with
+    ``eta_min = min_ratio * base``, held at ``min_ratio`` from ``total_steps`` on), ``linear`` (down to ``min_ratio`` over
+    ``total_steps``) or ``step`` (``StepLR(step_size, gamma)``), counted from the end of the warm-up.  ``factor(s)`` is the
+    factor of the update that follows ``s`` applied updates (torch's convention: ``scheduler.step()`` behind
+    ``optimizer.step()``); the kernel (coma_adamw_sched) evaluates the same definition in fp32 on the device."""
+
+    KINDS = ops.SCHED_KINDS
+
+    def __init__(self, warmup_steps=0, warmup_start=1.0 / 3.0, decay="constant", total_steps=None, min_ratio=0.0,
+                 step_size=None, gamma=0.1):
+        def whole(x):
+            return not isinstance(x, bool) and isinstance(x, int)
+
+        def real(x):
+            return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
+        if not whole(warmup_steps) or warmup_steps < 0 or warmup_steps >= 2 ** 31:
+            raise ValueError(f"warmup_steps must be an integer >= 0, got {warmup_steps!r}")
+        if not real(warmup_start) or not 0.0 < warmup_start <= 1.0:
+            raise ValueError(f"warmup_start must lie inside (0, 1], got {warmup_start!r}")
+        if decay not in self.KINDS:
+            raise ValueError(f"decay must be one of {self.KINDS}, got {decay!r}")
+        if decay in ("cosine", "linear"):
+            if not whole(total_steps) or total_steps < 1 or total_steps >= 2 ** 31:
+                raise ValueError(f"decay={decay!r} needs total_steps, an integer >= 1, got {total_steps!r}")
+        elif total_steps is not None and (not whole(total_steps) or total_steps < 1 or total_steps >= 2 ** 31):
+            raise ValueError(f"total_steps must be None or an integer >= 1, got {total_steps!r}")
+        if not real(min_ratio) or not 0.0 <= min_ratio <= 1.0:
+            raise ValueError(f"min_ratio must lie inside [0, 1], got {min_ratio!r}")
+        if decay == "step":
+            if not whole(step_size) or step_size < 1 or step_size >= 2 ** 31:
+                raise ValueError(f"decay='step' needs step_size, an integer >= 1, got {step_size!r}")
+        elif step_size is not None and (not whole(step_size) or step_size < 1 or step_size >= 2 ** 31):
+            raise ValueError(f"step_size must be None or an integer >= 1, got {step_size!r}")
+        if not real(gamma) or not 0.0 < gamma <= 1.0:
+            raise ValueError(f"gamma must lie inside (0, 1], got {gamma!r}")
+        self.warmup_steps, self.warmup_start, self.decay = warmup_steps, float(warmup_start), decay
+        self.total_steps, self.min_ratio, self.step_size, self.gamma = total_steps, float(min_ratio), step_size, float(gamma)
+
+    def factor(self, s):
+        """warm(s) * decay(u) in Python floats: the definition (the only place the formula lives on the host)."""
+        s = max(int(s), 0)
+        Wm, f0, T, r = self.warmup_steps, self.warmup_start, self.total_steps, self.min_ratio
+        warm = f0 + (1.0 - f0) * min(s, Wm) / Wm if Wm > 0 else 1.0
+        u = max(s - Wm, 0)
+        if self.decay != "step" and T is not None:
+            u = min(u, T)
+        if self.decay == "cosine":
+            dec = r + (1.0 - r) * (1.0 + math.cos(math.pi * u / T)) / 2.0
+        elif self.decay == "linear":
+            dec = 1.0 - (1.0 - r) * u / T
+        elif self.decay == "step":
+            dec = self.gamma ** (u // self.step_size)
+        else:
+            dec = 1.0
+        return warm * dec
+
+    def kernel_args(self):
+        """(kind, warmup_steps, warmup_start, total_steps, min_ratio, step_size, gamma) as ops.adamw_sched_ takes them."""
+        return (self.KINDS.index(self.decay), self.warmup_steps, self.warmup_start, self.total_steps or 1, self.min_ratio,
+                self.step_size or 1, self.gamma)
+
+    def to_dict(self):
+        return dict(warmup_steps=self.warmup_steps, warmup_start=self.warmup_start, decay=self.decay,
+                    total_steps=self.total_steps, min_ratio=self.min_ratio, step_size=self.step_size, gamma=self.gamma)
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**d)
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return "LRSchedule(" + ", ".join(f"{k}={v!r}" for k, v in self.to_dict().items()) + ")"
+
+
+def _as_schedule_dict(lr_schedule):
+    """None, an LRSchedule or a dict of its arguments -> None or the validated plain dict kept in param_groups[0]."""
+    if lr_schedule is None:
+        return None
+    if isinstance(lr_schedule, LRSchedule):
+        return lr_schedule.to_dict()
+    if isinstance(lr_schedule, dict):
+        try:
+            return LRSchedule(**lr_schedule).to_dict()
+        except TypeError as e:
+            raise ValueError(f"lr_schedule: {e}") from None
+    raise ValueError(f"lr_schedule must be None, an LRSchedule or a dict of its arguments, got {lr_schedule!r}")
+
+
+def _check_option(lr_scale, weight_decay, who=""):
+    ok = lambda x: not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and x >= 0.0
+    if not ok(lr_scale):
+        raise ValueError(f"param_options{who}: lr_scale must be a finite number >= 0, got {lr_scale!r}")
+    if weight_decay is not None and not ok(weight_decay):
+        raise ValueError(f"param_options{who}: weight_decay must be None or a finite number >= 0, got {weight_decay!r}")
+    return (float(lr_scale), None if weight_decay is None else float(weight_decay))
+
+
+def resolve_param_options(param_options, named_params):
+    """param_options -> None or the list of (lr_scale, weight_decay) pairs, aligned with `named_params` ([(name, param)]),
+    that param_groups[0] keeps; weight_decay None: the group's.  "no_decay_1d": weight decay 0 for every parameter with
+    ndim <= 1 (biases, norm scales, PReLU slopes, the learned prompts); a callable (name, param) -> dict(lr_scale=1.0,
+    weight_decay=None) (or None for the defaults); a ready list of pairs is checked and passed through."""
+    named_params = list(named_params)
+    if param_options is None:
+        return None
+    if isinstance(param_options, str):
+        if param_options != "no_decay_1d":
+            raise ValueError(f'param_options: the one preset is "no_decay_1d", got {param_options!r}')
+        return [(1.0, 0.0 if p.ndim <= 1 else None) for _, p in named_params]
+    if callable(param_options):
+        out = []
+        for name, p in named_params:
+            d = param_options(name, p) or {}
+            if not isinstance(d, dict) or set(d) - {"lr_scale", "weight_decay"}:
+                raise ValueError(f"param_options({name!r}) must return a dict with lr_scale / weight_decay, got {d!r}")
+            out.append(_check_option(d.get("lr_scale", 1.0), d.get("weight_decay"), f"({name!r})"))
+        return out
+    if isinstance(param_options, (list, tuple)):
+        if len(param_options) != len(named_params) or any(not isinstance(o, (list, tuple)) or len(o) != 2 for o in param_options):
+            raise ValueError(f"param_options: a list needs one (lr_scale, weight_decay) pair per parameter "
+                             f"({len(named_params)}), got {len(param_options)} entries")
+        return [_check_option(a, b, f"[{i}]") for i, (a, b) in enumerate(param_options)]
+    raise ValueError(f'param_options must be None, "no_decay_1d", a callable or a list of pairs, got {param_options!r}')
+
+
+def build_segments(numels, options, weight_decay, total=None, cap=ops.MAX_SEGS):
+    """The segment table of coma_adamw_sched for tensors of `numels` elements laid out back to back, with `options`
+    [(lr_scale, weight_decay or None)] beside them: -> (seg_end, seg_lr_scale, seg_wd) as lists, seg_end strictly ascending.
+    Neighbours with equal options are one segment, empty tensors none; the last segment reaches `total` (the flat buffer's
+    padding belongs to it).  ValueError above `cap` segments (the kernel's)."""
+    ends, scales, wds = [], [], []
+    pos = 0
+    for k, (scale, wd) in zip(numels, options):
+        if k == 0:
+            continue
+        pos += int(k)
+        opt = (float(scale), float(weight_decay if wd is None else wd))
+        if ends and (scales[-1], wds[-1]) == opt:
+            ends[-1] = pos
+        else:
+            ends.append(pos); scales.append(opt[0]); wds.append(opt[1])
+    if ends and total is not None:
+        assert total >= pos
+        ends[-1] = int(total)
+    if len(ends) > cap:
+        raise ValueError(f"param_options: {len(ends)} segments of the flat buffer differ from their neighbours, the kernel "
+                         f"takes at most {cap}: give neighbouring parameters equal options")
+    return ends, scales, wds
+
+
 def check_no_exchange(optimizer, reducer):
     """ValueError when a gradient exchange meets an optimizer that accumulates or clips."""
     if reducer is not None and getattr(optimizer, "windowed", False):
@@ -59,7 +221,8 @@ def check_no_exchange(optimizer, reducer):
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, dynamic=(), write_through=False,
-                 pad_to=1, grad_acc_batch=1, max_grad_norm=None, ema_decay=None, ema_warmup=False):
+                 pad_to=1, grad_acc_batch=1, max_grad_norm=None, ema_decay=None, ema_warmup=False, lr_schedule=None,
+                 param_options=None, param_names=None):
         """grad_acc_batch=K > 1: ``step()`` means "this micro-batch's backward is done" -- it adds the flat gradient to a flat
         fp32 accumulator and the K-th call (or ``flush()``) applies ONE update with the MEAN of the window's gradients.
         max_grad_norm: clip that mean gradient to this global 2-norm first (``torch.nn.utils.clip_grad_norm_``; the
@@ -68,12 +231,29 @@ class FusedAdamW(torch.optim.Optimizer):
         inside the update's own kernel (``ops.adamw_ema_``); d_t = d, or min(d, (1 + t) / (10 + t)) with ema_warmup (t: the
         update count).  The average starts at the parameters' values when the option is switched on.  ``swap_ema()`` /
         ``ema_weights()`` put it under the model, ``ema_state_dict`` / ``load_ema_state_dict`` serialise it.  Both options
-        live in ``param_groups[0]`` too."""
+        live in ``param_groups[0]`` too.
+        lr_schedule (None, an LRSchedule or a dict of its arguments) / param_options (None, "no_decay_1d", a callable
+        (name, param) -> dict(lr_scale=1.0, weight_decay=None), or a list of such pairs; param_names: the names the callable
+        sees, default the parameters' positions): either one switches the update to coma_adamw_sched, which forms
+        lr_t = lr * warm * decay on the device from the update count and takes lr_t * lr_scale and weight_decay per
+        parameter.  ``param_groups[0]`` keeps them as plain data -- the schedule's dict, a list of (lr_scale, weight_decay)
+        aligned with ``params`` -- so ``state_dict()`` carries them; ``param_groups[0]["lr"]`` stays the BASE rate, the one a
+        plateau scheduler acts on (``sync_lr()``), ``last_lr`` is the device float the kernel wrote and ``current_lr()`` the
+        host's value for logging."""
         _check_window_opts(grad_acc_batch, max_grad_norm)
         _check_ema_opts(ema_decay, ema_warmup)
+        params = list(params)
+        assert not params or not isinstance(params[0], dict), "one parameter group (the reference uses one)"
+        names = list(param_names) if param_names is not None else [str(i) for i in range(len(params))]
+        if len(names) != len(params):
+            raise ValueError(f"param_names: {len(names)} names for {len(params)} parameters")
+        lr_schedule = _as_schedule_dict(lr_schedule)
+        param_options = resolve_param_options(param_options, zip(names, params))
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_acc_batch=int(grad_acc_batch),
                         max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
                         ema_decay=None if ema_decay is None else float(ema_decay), ema_warmup=bool(ema_warmup))
+        if lr_schedule is not None or param_options is not None:      # (without the options the group has the keys it had)
+            defaults.update(lr_schedule=lr_schedule, param_options=param_options)
         super().__init__(params, defaults)
         assert len(self.param_groups) == 1, "one parameter group (the reference uses one)"
         self._dynamic = {id(p) for p in dynamic}   # may or may not get a gradient, step to step
@@ -110,6 +290,13 @@ class FusedAdamW(torch.optim.Optimizer):
         self._loose_ema = {}           # parameter outside the flat buffer -> its average (flat fp32), from its first step on
         self._ema_parked = {}          # parameter -> average loaded before the flat layout existed (load_ema_state_dict)
         self._ema_in = False           # swap_ema(): the parameters hold the average, flat_ema / _loose_ema the iterate
+        # learning-rate schedule / parameter options (allocated by _ensure_sched; none of it exists on the default path)
+        self._lr_dev = None            # device fp32: the base rate the kernel reads
+        self._lr_host = None           # its host shadow (sync_lr)
+        self.last_lr = None            # device fp32: the rate coma_adamw_sched formed for the last update (before any lr_scale)
+        self._seg_tab = None           # (seg_end int64, seg_lr_scale fp32, seg_wd fp32) on the device, or None: uniform
+        self._seg_key = None           # what the table was built from: (copy of the options list, weight decay)
+        self._index = None             # id(parameter) -> position in the group (_param_index)
 
     # -- layout -------------------------------------------------------------------------
     def _build(self):
@@ -147,6 +334,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._flat_step = max(self._flat_step, int(st["step"]))
         self._step_dev = torch.full((1,), self._flat_step, dtype=torch.int32, device=dev)
         self._ensure_ema()
+        self._ensure_sched()
 
     @property
     def built(self):
@@ -198,6 +386,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if not self.built:
             self._build()
         self._ensure_ema()
+        self._ensure_sched()
         if advance:
             self._flat_step += 1
             self._step_dev += 1            # device-side copy: a captured step keeps counting under graph replay
@@ -206,7 +395,7 @@ class FusedAdamW(torch.optim.Optimizer):
             if k > 0:                      # (elementwise: the average moves slice by slice with the parameters)
                 sl = slice(off, off + k)
                 self._update(self.flat_p[sl], self.flat_g[sl], self.flat_m[sl], self.flat_v[sl],
-                             self.flat_ema[sl] if averaging else None, self._flat_step, self._step_dev)
+                             self.flat_ema[sl] if averaging else None, self._flat_step, self._step_dev, flat_off=off)
         if not loose:
             return
         # backward is over: every slice of the step's zeroed arena is dead -- ONE memset clears them.  Behind the AdamW launch,
@@ -218,13 +407,29 @@ class FusedAdamW(torch.optim.Optimizer):
                 continue
             st = self._loose_state(p)
             self._update(p.data.view(-1), p.grad.float().contiguous().view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
-                         self._loose_average(p) if averaging else None, st["step"])
+                         self._loose_average(p) if averaging else None, st["step"], loose=p)
 
-    def _update(self, p, g, m, v, average, step, step_dev=None, window=None):
+    def _update(self, p, g, m, v, average, step, step_dev=None, window=None, flat_off=None, loose=None):
         """One update of the flat fp32 (p, g, m, v) and, where there is one, of `average`, at update count `step` / the device
         int32 `step_dev`.  window: ops.adamw_ex_'s (count_dev, partials, n_partials, extra_sumsq, max_norm, norm_out), or None
-        outside an accumulation window.  The one place that picks the kernel; the default step stays on coma_adamw."""
+        outside an accumulation window.  flat_off: (p, g, m, v) are the flat buffers from this element on; loose: they are
+        those of this parameter outside the flat buffer (only the scheduled path looks at either).  The one place that picks
+        the kernel; the default step stays on coma_adamw."""
         grp = self.param_groups[0]
+        if self.scheduled:
+            # all three variants in one entry point.  A slice of the flat buffer reads the segment table at its own offset;
+            # a loose parameter has its own options and bias-correction count, and the schedule's count is the global one
+            b1, b2 = grp["betas"]
+            scale, wd, segs = 1.0, grp["weight_decay"], None
+            if loose is not None:
+                scale, wd = self._option_of(loose)
+            elif self._seg_tab is not None:
+                segs = self._seg_tab
+            d, w = self._ema_opts() if average is not None else (0.0, False)
+            ops.adamw_sched_(p, g, m, v, self._lr_dev, self._schedule().kernel_args(), b1, b2, grp["eps"], wd, step, step_dev,
+                             self._flat_step, self._step_dev, scale, segs, flat_off or 0,
+                             self.last_lr if loose is None else None, average, d, w, *(window or ()))
+            return
         hp = (float(grp["lr"]), *grp["betas"], grp["eps"], grp["weight_decay"])
         if average is not None:
             ops.adamw_ema_(p, g, m, v, average, *self._ema_opts(), *hp, step, step_dev, *(window or ()))
@@ -282,6 +487,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._build()
         self._ensure_window_buffers()
         self._ensure_ema()
+        self._ensure_sched()
         self._sparse_zero_bookkeeping()
         apply = self._pending + 1 >= K
         nb = None
@@ -312,6 +518,7 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError(EMA_IN.format("flush()"))
         K, mx = self._window_opts()
         self._ensure_ema()
+        self._ensure_sched()
         with torch.no_grad():
             self._apply(K, mx, None)
 
@@ -338,12 +545,12 @@ class FusedAdamW(torch.optim.Optimizer):
         averaging = self.averaging         # the average moves here, on the applying update, never on a micro-batch
         window = (count_dev, partials, n_part, extra, mx or 0.0)
         self._update(self.flat_p, src, self.flat_m, self.flat_v, self.flat_ema if averaging else None, self._flat_step,
-                     self._step_dev, window + (norm_out,))
+                     self._step_dev, window + (norm_out,), flat_off=0)
         ops.ZeroArena.end_step()           # (behind the sweep, as in step_shards)
         for p, a in loose_src:
             st = self._loose_state(p)
             self._update(p.data.view(-1), a, st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1),
-                         self._loose_average(p) if averaging else None, st["step"], None, window + (None,))
+                         self._loose_average(p) if averaging else None, st["step"], None, window + (None,), loose=p)
         if acc_mode:
             self._acc_dev.zero_()
             for _, a in loose_src:
@@ -351,6 +558,81 @@ class FusedAdamW(torch.optim.Optimizer):
             self._loose_live.clear()
         self._pending = 0
         self.last_grad_norm = norm_out
+
+    # -- learning-rate schedule and parameter options ---------------------------------------
+    @property
+    def scheduled(self):
+        """lr_schedule or param_options is set: every update goes through coma_adamw_sched."""
+        g = self.param_groups[0]
+        return g.get("lr_schedule") is not None or g.get("param_options") is not None
+
+    def _schedule(self):
+        d = self.param_groups[0].get("lr_schedule")
+        return LRSchedule() if d is None else LRSchedule.from_dict(d)
+
+    def _option_of(self, p):
+        """(lr_scale, weight_decay) of one parameter of the group."""
+        g = self.param_groups[0]
+        opts = g.get("param_options")
+        if opts is None:
+            return 1.0, g["weight_decay"]
+        scale, wd = opts[self._param_index()[id(p)]]
+        return float(scale), float(g["weight_decay"] if wd is None else wd)
+
+    def _param_index(self):
+        """id(parameter) -> its position in the group (the group's parameter list never changes)."""
+        if self._index is None:
+            self._index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        return self._index
+
+    def _ensure_sched(self):
+        """The device state of the scheduled path -- base rate, last_lr, segment table -- allocated outside any graph capture
+        (GraphedTrainStep._capture calls this first), and the base rate brought up to date (sync_lr)."""
+        if not self.built or not self.scheduled:
+            return
+        g = self.param_groups[0]
+        dev = self.flat_p.device
+        if self._lr_dev is None:
+            self._lr_host = float(g["lr"])
+            self._lr_dev = torch.full((1,), self._lr_host, dtype=torch.float32, device=dev)
+            self.last_lr = torch.zeros(1, dtype=torch.float32, device=dev)
+        opts = g.get("param_options")
+        # (compared by value against a copy: the list may be edited in place; no tuple is built while nothing changed)
+        same = (opts is None and self._seg_key is None) or \
+            (opts is not None and self._seg_key is not None and self._seg_key[1] == g["weight_decay"] and self._seg_key[0] == opts)
+        if not same:
+            if opts is not None:
+                opts[:] = [tuple(o) for o in opts]          # (pairs that came as lists would never compare equal to the copy)
+            self._seg_key = None if opts is None else (list(opts), float(g["weight_decay"]))
+            self._seg_tab = None
+            if opts is not None:
+                if len(opts) != len(g["params"]):
+                    raise ValueError(f"param_options: {len(opts)} entries for {len(g['params'])} parameters")
+                index = self._param_index()
+                ends, scales, wds = build_segments([p.numel() for p in self._flat_params],
+                                                   [opts[index[id(p)]] for p in self._flat_params], g["weight_decay"],
+                                                   total=self.flat_p.numel())
+                self._seg_tab = (torch.tensor(ends, dtype=torch.int64, device=dev),
+                                 torch.tensor(scales, dtype=torch.float32, device=dev),
+                                 torch.tensor(wds, dtype=torch.float32, device=dev))
+        self.sync_lr()
+
+    def sync_lr(self):
+        """param_groups[0]["lr"] -> the device float the kernel reads, when it differs from what is there (a plateau
+        scheduler moved it).  Never inside a capture: step() calls it when not capturing, GraphedTrainStep before a replay."""
+        if self._lr_dev is None or torch.cuda.is_current_stream_capturing():
+            return
+        lr = float(self.param_groups[0]["lr"])
+        if lr != self._lr_host:
+            self._lr_dev.fill_(lr)
+            self._lr_host = lr
+
+    def current_lr(self):
+        """The host's value of the rate of the NEXT update, lr * factor(applied updates): for logging, no device read."""
+        count = self._flat_step
+        if not self.built:                # (a loaded state waits in self.state until the layout exists: _build takes its count)
+            count = max([count] + [int(st["step"]) for st in self.state.values() if st])
+        return float(self.param_groups[0]["lr"]) * self._schedule().factor(count)
 
     # -- weight EMA ------------------------------------------------------------------------
     def _ema_opts(self):
@@ -529,6 +811,8 @@ class FusedAdamW(torch.optim.Optimizer):
         params = self.param_groups[0]["params"]
         # (a file written without an average does not switch off the one this optimizer was built with)
         skip = ("params", "ema_decay", "ema_warmup") if sd["param_groups"][0].get("ema_decay") is None else ("params",)
+        # (nor does one written without a schedule or without parameter options switch off what this one has)
+        skip += tuple(k for k in ("lr_schedule", "param_options") if sd["param_groups"][0].get(k) is None)
         for k, v in sd["param_groups"][0].items():
             if k not in skip:
                 self.param_groups[0][k] = v
@@ -547,3 +831,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                  "exp_avg_sq": st["exp_avg_sq"].to(p.device).float().clone()}
         if self.built:      # parameters inside the flat buffer share one step count
             self._step_dev.fill_(self._flat_step)
+        g = self.param_groups[0]
+        if g.get("lr_schedule") is not None:
+            g["lr_schedule"] = _as_schedule_dict(g["lr_schedule"])
+        if g.get("param_options") is not None:
+            g["param_options"] = resolve_param_options([tuple(o) for o in g["param_options"]], [(str(i), p) for i, p in enumerate(params)])

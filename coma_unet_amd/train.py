@@ -15,17 +15,22 @@ from .data_parallel import GradReducer, StreamedGradExchange
 
 
 def make_optimizer(model, lr=1e-3, write_through=True, pad_to=1, grad_acc_batch=1, max_grad_norm=None, ema_decay=None,
-                   ema_warmup=False):
+                   ema_warmup=False, lr_schedule=None, param_options=None):
     """torch.optim.AdamW(model.parameters(), lr) of :736, fused.  ``write_through``: parameter gradients are
     written by the backward kernels straight into the optimizer's flat gradient buffer (see ops.GradSink).
     ``pad_to``: the world size when the step is sharded over ranks (StreamedGradExchange(sharded=True)).
     ``grad_acc_batch`` / ``max_grad_norm``: one update per grad_acc_batch steps with the mean of their gradients, clipped
     to that global norm (optim.FusedAdamW; the reference's commented-out accumulation, :887-890, :918-920).
     ``ema_decay`` / ``ema_warmup``: an exponential moving average of the weights kept by the update's own kernel
-    (``optimizer.ema_weights()``, ``ema_state_dict``)."""
+    (``optimizer.ema_weights()``, ``ema_state_dict``).
+    ``lr_schedule`` (an ``optim.LRSchedule`` or a dict of its arguments) / ``param_options`` ("no_decay_1d" or a callable
+    (name, param) -> dict(lr_scale=1.0, weight_decay=None), called with the names of ``model.named_parameters()``): the
+    learning rate is formed on the device per update, and lr_scale / weight_decay apply per parameter (optim.FusedAdamW)."""
     dyn = [model.pos_dynamic_prompt, model.neg_dynamic_prompt] if not getattr(model, "static_prompts", False) else []
-    return FusedAdamW(model.parameters(), lr=lr, dynamic=dyn, write_through=write_through, pad_to=pad_to,
-                      grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)
+    named = list(model.named_parameters())
+    return FusedAdamW([p for _, p in named], lr=lr, dynamic=dyn, write_through=write_through, pad_to=pad_to,
+                      grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                      lr_schedule=lr_schedule, param_options=param_options, param_names=[n for n, _ in named])
 
 
 def forward_loss(model, criterion, batch, global_rnc=False):
@@ -111,8 +116,15 @@ class GraphedTrainStep:
 
     def _hyper(self):
         g = self.optimizer.param_groups[0]
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), g.get("grad_acc_batch", 1),
-                g.get("max_grad_norm"), g.get("ema_decay"), bool(g.get("ema_warmup", False)))
+        hyper = (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), g.get("grad_acc_batch", 1),
+                 g.get("max_grad_norm"), g.get("ema_decay"), bool(g.get("ema_warmup", False)))
+        if getattr(self.optimizer, "scheduled", False):
+            # the base rate lives in device memory there (optimizer.sync_lr): a new value needs no new capture.  The
+            # schedule's scalars and the parameter options are kernel arguments and table contents: those still do
+            sched, opts = g.get("lr_schedule"), g.get("param_options")
+            hyper = (None,) + hyper[1:] + (None if sched is None else tuple(sorted(sched.items())),
+                                           None if opts is None else tuple(tuple(o) for o in opts))
+        return hyper
 
     def _capture(self):
         """(Re)capture.  The optimizer's hyper-parameters are kernel arguments frozen into the graph, so a change of
@@ -126,6 +138,8 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         self.micro_graph = None
         optimizer._ensure_ema()          # (ema_decay switched on since the last step: the average is allocated out here)
+        if hasattr(optimizer, "_ensure_sched"):
+            optimizer._ensure_sched()    # (likewise the base rate, last_lr and the segment table of a scheduled optimizer)
         K = int(optimizer.param_groups[0].get("grad_acc_batch", 1))
         if K > 1:
             return self._capture_window(K)
@@ -183,6 +197,8 @@ class GraphedTrainStep:
         whole = self.reducer is None or self.in_graph
         if whole and self._hyper() != self._captured_hyper:
             self._capture()
+        if getattr(self.optimizer, "scheduled", False):
+            self.optimizer.sync_lr()     # a plateau scheduler's new base rate reaches the device float the replay reads
         if self.micro_graph is not None:
             opt = self.optimizer
             if opt.pending + 1 < self._captured_hyper[4]:          # not the window's last micro-batch

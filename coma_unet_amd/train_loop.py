@@ -133,6 +133,12 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        under the averaged weights (``optimizer.ema_weights()``: swapped in by content and back out, BatchNorm running
        statistics stay the iterate's); a ``predictor=`` passed through is ``refresh()``ed inside and again after.  Every
        checkpoint carries the average as ``"ema_state_dict"``.  Not available under a sharded exchange (ValueError).
+     * ``lr_schedule`` / ``param_options`` (None / None): passed to ``make_optimizer`` when the optimizer is built here -- a
+       per-update learning-rate schedule (``optim.LRSchedule`` or a dict of its arguments: linear warm-up, then constant /
+       cosine / linear / step decay) evaluated by the update's own kernel at the device update count, and per-parameter
+       ``lr_scale`` / ``weight_decay`` ("no_decay_1d", or a callable (name, param) -> dict).  ``lr`` is then the BASE rate:
+       the plateau scheduler below keeps acting on it, and a replayed graph picks the new value up without a new capture.
+       The epoch's log line carries ``optimizer.current_lr()``; checkpoints carry both options in the optimizer's state.
      * ``freeze_bn``: when given, ``model.freeze_batchnorm(freeze_bn)`` before the first epoch (else the model stays as
        the caller set it) -- every BatchNorm3d normalises with its running statistics and leaves them alone (fine-tuning
        a resumed checkpoint); the switch survives the ``model.train(True)`` of every epoch.
@@ -195,7 +201,8 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
             optimizer = reducer.opt           # the reducer buckets THIS optimizer's flat gradient buffer
         else:
             optimizer = make_optimizer(model, lr, grad_acc_batch=grad_acc_batch, max_grad_norm=max_grad_norm,
-                                       ema_decay=kwargs.get("ema_decay"), ema_warmup=kwargs.get("ema_warmup", False))
+                                       ema_decay=kwargs.get("ema_decay"), ema_warmup=kwargs.get("ema_warmup", False),
+                                       lr_schedule=kwargs.get("lr_schedule"), param_options=kwargs.get("param_options"))
         for g in optimizer.param_groups:
             g["lr"] = lr
         scheduler = ReduceLROnPlateau(optimizer, "min", patience=5)
@@ -293,7 +300,8 @@ def _train_epochs(model, criterion, train_loader, validation_loader, epochs, sav
         if rank == 0:
             logging.info(f"epoch {epoch}: avg loss {epoch_loss / num_samples:.6f} (gen {epoch_gen / num_samples:.6f}, "
                          f"pred-contra {epoch_pred / num_samples:.6f}, ds-contra {epoch_ds / num_samples:.6f}; "
-                         f"pos {epoch_pos / max(n_pos, 1):.6f}, neg {epoch_neg / max(n_neg, 1):.6f})")
+                         f"pos {epoch_pos / max(n_pos, 1):.6f}, neg {epoch_neg / max(n_neg, 1):.6f})"
+                         + (f", lr {optimizer.current_lr():.9e}" if getattr(optimizer, "scheduled", False) else ""))
         if save_path:                                                                                     # :943-955
             # every rank assembles the dict (FusedAdamW.state_dict() all-gathers sharded moments), rank 0 writes it
             save_checkpoint(save_path, epoch, model, optimizer, loss, scheduler, checkpoint_iter=checkpoint_iter, write=rank == 0,

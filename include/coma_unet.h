@@ -460,6 +460,46 @@ int coma_adamw_ema(float* p, const float* g, float* m, float* v, int64_t n, floa
                    const int32_t* count_dev, const double* partials, int32_t n_partials,
                    const double* extra_sumsq, float max_norm, float* norm_out, float* ema, float ema_decay,
                    int32_t ema_warmup, void* stream);
+/* ---- learning-rate schedule and per-segment options inside the same sweep (FusedAdamW(lr_schedule, param_options)).
+ * coma_adamw_sched: coma_adamw_ema with the same arguments (ema == NULL: coma_adamw_ex, ema_decay / ema_warmup unused),
+ *   except that the learning rate of this update is formed on the device, once per block, in fp32:
+ *       t = *sched_step_dev, else sched_step, else (both zero) the update count *step_dev / step;   s = t - 1
+ *       warm  = warmup_start + (1 - warmup_start) * min(s, warmup_steps) / warmup_steps      (1 when warmup_steps == 0)
+ *       u     = s - warmup_steps clamped to [0, total_steps]  (SCHED step: from below only)
+ *       decay = 1                                                                 sched_kind 0, constant
+ *               min_ratio + (1 - min_ratio) (1 + cos(pi u / total_steps)) / 2     sched_kind 1, cosine
+ *               1 - (1 - min_ratio) u / total_steps                               sched_kind 2, linear
+ *               gamma ^ floor(u / step_size)                                      sched_kind 3, step
+ *       lr_t  = *lr_dev * warm * decay
+ *   (torch's LinearLR(start_factor, total_iters) followed by CosineAnnealingLR / StepLR with scheduler.step() behind
+ *   optimizer.step(); cosf and powf, no fast intrinsics).  A replayed graph walks through the schedule, and a new value in
+ *   *lr_dev (a plateau scheduler) takes effect without a new capture.  sched_step / sched_step_dev are separate from step /
+ *   step_dev so that a tensor with its own bias-correction count still follows the global schedule.  lr_out (device fp32,
+ *   may be NULL): block 0 stores lr_t, before any scale.
+ *   Element i has flat coordinate elem_base + i and belongs to the first segment k with seg_end[k] > coordinate (the last
+ *   one beyond the table's end); it is updated with lr_t * seg_lr_scale[k] and the decay seg_wd[k].  seg_end (device int64)
+ *   must be strictly ascending: the caller's contract, not checked on the device.  n_segs == 0: lr_t * lr_scale and
+ *   weight_decay for every element.  n_segs <= 2048; the table is staged in LDS (16 bytes per segment and block).  Segments
+ *   shorter than a 16-byte chunk and boundaries inside one are allowed.  With lr_scale == 1 and n_segs == 0 the results are
+ *   bitwise those of coma_adamw / coma_adamw_ex / coma_adamw_ema called with lr = *lr_out, path by path: the 16-byte loop
+ *   (all buffers 16-byte aligned, elements below 4 * (n / 4)) is bitwise their 16-byte loop, the scalar loop (its tail, and
+ *   every element of a call with an unaligned buffer) bitwise their scalar loop.  As in those kernels the two loops do NOT
+ *   give the same bits as each other: the 16-byte loop fuses each moment update into one fma, the scalar loop rounds its
+ *   product and its sum separately.  So a slice passed with elem_base is bitwise the same elements of a whole launch only
+ *   where every element stays on its loop -- the slice starts and, unless it reaches the end, ends at a multiple of four
+ *   elements of 16-byte aligned buffers -- and differs in the last bits of m, v (and then p) otherwise.
+ *   Checked before any launch: lr_dev non-NULL, sched_kind in [0, 4),
+ *   total_steps >= 1 for cosine and linear, step_size >= 1, 0 < gamma <= 1, 0 <= min_ratio <= 1, 0 < warmup_start <= 1,
+ *   warmup_steps >= 0, n_segs in [0, 2048].  n == 0: no launch, nothing written. ---- */
+int coma_adamw_sched(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
+                     float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                     const int32_t* count_dev, const double* partials, int32_t n_partials,
+                     const double* extra_sumsq, float max_norm, float* norm_out, float* ema, float ema_decay,
+                     int32_t ema_warmup, int32_t sched_kind, int32_t warmup_steps, float warmup_start,
+                     int32_t total_steps, float min_ratio, int32_t step_size, float gamma, int32_t sched_step,
+                     const int32_t* sched_step_dev, float lr_scale, const int64_t* seg_end,
+                     const float* seg_lr_scale, const float* seg_wd, int32_t n_segs, int64_t elem_base,
+                     float* lr_out, void* stream);
 /* coma_swap_f32: exchange the CONTENTS of two disjoint device buffers of n floats (a[i] <-> b[i]); the addresses that
  *   parameter views and captured graphs hold stay valid.  a == b or overlapping ranges: error status, nothing launched.
  *   Same 16-byte / scalar paths as coma_adamw_ema.  n == 0: no launch. */
