@@ -101,6 +101,9 @@ SIGNATURES = {
     "coma_roi_mse_bwd": (_i32, [_TP, _TP, _vp, _vp, _TP, _vp]),
     "coma_l1_fwd": (_i32, [_TP, _TP, _vp, _vp, _sz, _vp]),
     "coma_l1_bwd": (_i32, [_TP, _TP, _vp, _TP, _vp]),
+    "coma_roi_wloss_ws_bytes": (_sz, [_TP]),
+    "coma_roi_wloss_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "coma_roi_wloss_bwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _f32, _vp, _vp, _TP, _vp]),
     "coma_eval_stats": (_i32, [_TP, _TP, _TP, _vp, _i32, _vp, _vp]),
     "coma_ssim_ws_bytes": (_sz, [_TP, _i32]),
     "coma_ssim_partial": (_i32, [_TP, _TP, _vp, _i32, _f32, _f32, _vp, _sz, _vp, _vp]),

@@ -2,7 +2,8 @@
 
 Same class names / call signatures as /root/reference/criterions.py:
 ``RoiMSE`` (:124-211), ``GenerativeContrastiveLoss`` (:485-575),
-``LabelDifference`` / ``FeatureSimilarity`` / ``RnCLoss`` (:579-644).  The voxel losses are
+``LabelDifference`` / ``FeatureSimilarity`` / ``RnCLoss`` (:579-644), and the two voxel-weighted alternatives the
+drivers keep at hand, ``RoiRRMSE`` / ``RoiRSE`` (:28-122), with ``RoiWeightedMSE`` beside them.  The voxel losses are
 fused HIP kernels (one pass: label->weight LUT, squared/absolute difference, per-sample
 reduction; gradient in one more pass).  RnC works on a (B, 512) feature matrix and a (B, 6)
 label matrix -- a few thousand numbers -- and stays as torch glue.
@@ -23,7 +24,21 @@ def _vol_internal(t: torch.Tensor, dtype=None):
     return v if dtype is None else v.to(dtype)
 
 
-class RoiMSE(nn.Module):
+class _RoiTables:
+    """Device-side ROI id / weight tables shared by the ROI losses."""
+
+    def _tables(self, dev):
+        """ROI id / weight tables on the device, rebuilt only when the weights object changes
+        (no host->device copy inside the step: keeps it hipGraph-capturable)."""
+        key = (dev, id(self.roi_weights), getattr(self.roi_weights, "_version", 0), tuple(self.roi_indices))
+        if getattr(self, "_tab_key", None) != key:
+            self._tab = (torch.as_tensor(list(self.roi_indices), dtype=torch.int32, device=dev),
+                         torch.as_tensor(self.roi_weights, dtype=torch.float32).to(dev).contiguous())
+            self._tab_key = key
+        return self._tab
+
+
+class RoiMSE(_RoiTables, nn.Module):
     """loss_b = mean_vox(mask_b) * mean_vox((pred_b - gt_b)^2), mask = ROI weight of each voxel's label."""
 
     def __init__(self, roi_weights, roi_indices, reduction="mean", scale_factor=360, voxel_wise=False, template=None):
@@ -77,16 +92,6 @@ class RoiMSE(nn.Module):
     def update_weights(self, weights):   # criterions.py:170-172 (a no-op upstream)
         return
 
-    def _tables(self, dev):
-        """ROI id / weight tables on the device, rebuilt only when the weights object changes
-        (no host->device copy inside the step: keeps it hipGraph-capturable)."""
-        key = (dev, id(self.roi_weights), getattr(self.roi_weights, "_version", 0), tuple(self.roi_indices))
-        if getattr(self, "_tab_key", None) != key:
-            self._tab = (torch.as_tensor(list(self.roi_indices), dtype=torch.int32, device=dev),
-                         torch.as_tensor(self.roi_weights, dtype=torch.float32).to(dev).contiguous())
-            self._tab_key = key
-        return self._tab
-
     def forward(self, pred, gt, roi):
         dev = pred.device
         p = _vol_internal(pred)
@@ -109,6 +114,103 @@ class RoiMSE(nn.Module):
         if self.batch_reduction == "mean":
             return torch.mean(loss)
         return loss
+
+
+class _RoiVoxelWeighted(_RoiTables, nn.Module):
+    """The voxel-weighted ROI losses (one fused reduction + one streaming backward, csrc/roi_loss.hip): every voxel's
+    squared error is weighted by w_v = roi_weights[slot of its label], or `background_weight` where the label is not in
+    `roi_indices` (the reference starts its mask from torch.ones: 1).  Per sample, N = sum w (pred - gt)^2 and
+        RoiWeightedMSE  N / sum w
+        RoiRSE          N / sum (gt - m)^2,  m = mean(w gt)     (criterions.py:101-121)
+        RoiRRMSE        sqrt(N / sum w gt^2)                    (criterions.py:40-67)
+    RoiRSE's denominator is the reference's: UNWEIGHTED, about the weighted "mean" m (:109-112).  No clamps: a zero
+    denominator, or a zero numerator under RoiRRMSE, gives inf / nan values or gradients exactly as the reference's
+    autograd does.  The target gets no gradient.
+
+    `reduction` ("mean": batch mean; "sum", as the reference for anything but "mean": batch sum; None: the per-sample
+    (B, 1) vector, what train_dp sets) is also readable and writable as `batch_reduction`, the attribute the training
+    loop, GenerativeContrastiveLoss and WithSSIM use."""
+
+    KIND = None
+    voxel_wise = False
+    voxel_weights = None
+
+    def __init__(self, roi_weights, roi_indices, reduction="mean", background_weight=1.0, scale_factor=360):
+        super().__init__()
+        name = type(self).__name__
+        if reduction not in ("mean", "sum", None):
+            raise ValueError(f"{name}: reduction must be 'mean', 'sum' or None, got {reduction!r}")
+        n = len(roi_indices)
+        if not 1 <= n <= 64:
+            raise ValueError(f"{name}: 1..64 ROI indices expected, got {n}")
+        if len(roi_weights) != n:
+            raise ValueError(f"{name}: {len(roi_weights)} weights for {n} ROI indices")
+        bg = float(background_weight)
+        if bg != bg or bg in (float("inf"), float("-inf")):
+            raise ValueError(f"{name}: background_weight must be finite, got {background_weight}")
+        self.roi_weights = roi_weights
+        self.roi_indices = roi_indices
+        self.batch_reduction = reduction
+        self.background_weight = bg
+        self.scale_factor = scale_factor
+
+    @property
+    def reduction(self):
+        return self.batch_reduction
+
+    @reduction.setter
+    def reduction(self, value):
+        self.batch_reduction = value
+
+    def __str__(self):
+        return (f"{type(self).__name__}(\n  roi_weights={self.roi_weights}\n  roi_indices={self.roi_indices}\n"
+                f"  reduction={self.batch_reduction}\n)")
+
+    calculate_new_weights = RoiMSE.calculate_new_weights      # criterions.py:154-159: what the training loop calls
+    update_weights = RoiMSE.update_weights                    # (a no-op upstream)
+
+    def forward(self, pred, gt, roi):
+        name = type(self).__name__
+        if roi is None:
+            raise ValueError(f"{name}: needs the ROI label volume")
+        if pred.dim() != 5 or pred.shape[1] != 1 or pred.shape != gt.shape or pred.shape != roi.shape:
+            raise ValueError(f"{name}: (B, 1, D, H, W) volumes of equal shape expected, got {tuple(pred.shape)}, "
+                             f"{tuple(gt.shape)}, {tuple(roi.shape)}")
+        ids, w = self._tables(pred.device)
+        p = _vol_internal(pred)
+        loss = ops.RoiWeightedLoss.apply(p, _vol_internal(gt.detach(), p.dtype).contiguous(),
+                                         _vol_internal(roi, torch.float32).contiguous(), ids, w,
+                                         self.background_weight, self.KIND)   # (B, 1)
+        if self.batch_reduction is None:
+            return loss
+        return torch.mean(loss) if self.batch_reduction == "mean" else torch.sum(loss)
+
+
+class RoiWeightedMSE(_RoiVoxelWeighted):
+    """sum_v w_v (pred - gt)^2 / sum_v w_v per sample."""
+
+    KIND = ops.RoiWeightedLoss.WMSE
+
+    def __init__(self, roi_weights, roi_indices, reduction="mean", background_weight=1.0):
+        super().__init__(roi_weights, roi_indices, reduction, background_weight)
+
+
+class RoiRSE(_RoiVoxelWeighted):
+    """Relative squared error weighted by ROI: the reference's class (criterions.py:82-121), constructor and forward."""
+
+    KIND = ops.RoiWeightedLoss.RSE
+
+    def __init__(self, roi_weights, roi_indices, reduction="mean"):
+        super().__init__(roi_weights, roi_indices, reduction)
+
+
+class RoiRRMSE(_RoiVoxelWeighted):
+    """Relative root mean squared error weighted by ROI: the reference's class (criterions.py:28-67)."""
+
+    KIND = ops.RoiWeightedLoss.RRMSE
+
+    def __init__(self, roi_weights, roi_indices, reduction="mean"):
+        super().__init__(roi_weights, roi_indices, reduction)
 
 
 class VoxelL1(nn.Module):
@@ -313,10 +415,18 @@ class GenerativeContrastiveLoss(nn.Module):
         return total, gen_loss, total_pred_space, total_ds
 
 
-def build_reference_criterion(device="cuda"):
-    """validation.py:130-154 with ``-rnc`` + attn_unet_data_parallel.py:717."""
+GEN_LOSSES = {"roi_mse": lambda w: RoiMSE(w, ROI_INDICES, voxel_wise=False), "roi_rse": lambda w: RoiRSE(w, ROI_INDICES),
+              "roi_rrmse": lambda w: RoiRRMSE(w, ROI_INDICES), "roi_wmse": lambda w: RoiWeightedMSE(w, ROI_INDICES)}
+
+
+def build_reference_criterion(device="cuda", gen_loss="roi_mse"):
+    """validation.py:130-154 with ``-rnc`` + attn_unet_data_parallel.py:717.  `gen_loss`: "roi_mse" (the live driver line,
+    validation.py:146) or one of the alternatives the reference keeps beside it (:132-133), "roi_rse" / "roi_rrmse", or
+    "roi_wmse"."""
+    if gen_loss not in GEN_LOSSES:
+        raise ValueError(f"build_reference_criterion: gen_loss must be one of {sorted(GEN_LOSSES)}, got {gen_loss!r}")
     w = torch.full((len(ROI_INDICES),), 225.0, device=device)
-    crit = GenerativeContrastiveLoss(RnCLoss(), RoiMSE(w, ROI_INDICES, voxel_wise=False),
+    crit = GenerativeContrastiveLoss(RnCLoss(), GEN_LOSSES[gen_loss](w),
                                      nn.TripletMarginLoss(1), regulatory_weight=0.0, ds_regulatory_weight=1.0)
     crit.gen_loss.batch_reduction = None
     return crit

@@ -1470,6 +1470,35 @@ class RoiMSELoss(Function):
         return dpred, None, None, None, None
 
 
+class RoiWeightedLoss(Function):
+    """The voxel-weighted ROI losses of csrc/roi_loss.hip (DESIGN.md section 4 "ROI-weighted losses"): per-sample loss
+    vector (B, 1) of kind 0 weighted MSE, 1 RoiRSE, 2 RoiRRMSE (criterions.py:28-122).  Saved besides the inputs: `coef`
+    (B floats); the backward kernel rebuilds every voxel's weight from the label table.  The target gets no gradient."""
+
+    WMSE, RSE, RRMSE = 0, 1, 2
+
+    @staticmethod
+    def forward(ctx, pred, gt, roi, roi_ids, roi_w, bg_weight, kind):
+        B = pred.shape[0]
+        cp = ct(pred)
+        loss, coef = _f32(B, pred.device), _f32(B, pred.device)
+        ws = workspace(lib.coma_roi_wloss_ws_bytes(cp), pred.device)
+        check(lib.coma_roi_wloss_fwd(cp, ct(gt), ct(roi), ptr(roi_ids), ptr(roi_w), roi_ids.numel(), float(bg_weight), int(kind),
+                                     ptr(loss), ptr(coef), ptr(ws), ws.numel(), L.stream()), "coma_roi_wloss_fwd")
+        ctx.save_for_backward(pred, gt, roi, roi_ids, roi_w, coef)
+        ctx.bg = float(bg_weight)
+        return loss.view(B, 1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, roi, roi_ids, roi_w, coef = ctx.saved_tensors
+        g = gout.contiguous().float().view(-1)
+        dpred = torch.empty_like(pred)
+        check(lib.coma_roi_wloss_bwd(ct(pred), ct(gt), ct(roi), ptr(roi_ids), ptr(roi_w), roi_ids.numel(), ctx.bg, ptr(g),
+                                     ptr(coef), ct(dpred), L.stream()), "coma_roi_wloss_bwd")
+        return dpred, None, None, None, None, None, None
+
+
 class L1Loss(Function):
     """Per-sample voxel MAE (the reference's evaluation metric, attn_unet_data_parallel.py:1215)."""
 

@@ -401,6 +401,23 @@ int coma_l1_fwd(const coma_tensor* pred, const coma_tensor* gt, float* loss, voi
 int coma_l1_bwd(const coma_tensor* pred, const coma_tensor* gt, const float* gout,
                 const coma_tensor* dpred, void* stream);
 
+/* ---- ROI-weighted voxel losses (criterions.py:28-122 RoiRRMSE / RoiRSE and the plain weighted MSE; csrc/roi_loss.hip) ----
+ * w_v = roi_w[slot of the voxel's label], bg_weight for a label outside roi_ids; d = pred - gt; N = sum_v w d^2
+ *   kind 0 WMSE   D = sum w                                               loss = N / D        coef = 2 / D
+ *   kind 1 RSE    D = sum g^2 - 2 m sum g + V m^2,  m = sum(w g) / V      loss = N / D        coef = 2 / D
+ *   kind 2 RRMSE  D = sum w g^2                                           loss = sqrt(N / D)  coef = 1 / (D loss)
+ * (RSE's D = sum (g - m)^2 is the reference's unweighted denominator about its weighted "mean", :109-112.)
+ * loss, coef: B floats.  No clamps: D = 0, or N = 0 under RRMSE, give inf / nan by IEEE arithmetic.
+ * pred / gt / dpred: one dtype (fp32 or bf16), C = 1; gt and roi (fp32) of voxel pitch 1.  No atomics, no host read. */
+size_t coma_roi_wloss_ws_bytes(const coma_tensor* pred);
+int coma_roi_wloss_fwd(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi,
+                       const int32_t* roi_ids, const float* roi_w, int32_t n_roi, float bg_weight, int32_t kind,
+                       float* loss, float* coef, void* ws, size_t ws_bytes, void* stream);
+/* dpred (=) gout[b] * coef[b] * w_v * (pred - gt); the target gets no gradient */
+int coma_roi_wloss_bwd(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi,
+                       const int32_t* roi_ids, const float* roi_w, int32_t n_roi, float bg_weight,
+                       const float* gout, const float* coef, const coma_tensor* dpred, void* stream);
+
 /* ---- evaluation statistics: one pass over (pred, gt, roi) giving, per sample and per
  *      bin (n_roi ROIs + the whole volume), the sums behind calc_roi_metrics (attn_unet_data_parallel.py:1361-1397),
  *      the global MAE/MAPE/RSE/RRMSE of contrastive_test (:1214-1231) and RoiCorrMetric (:49-60).
