@@ -9,6 +9,7 @@ from .attn_unet_data_parallel import (ContrastiveAttentionUNET_DP, ObservableAtt
 from .inference import Predictor, fold_gate
 from .optim import FusedAdamW, LRSchedule
 from .criterions import RoiRSE, RoiRRMSE, RoiWeightedMSE  # noqa: F401
+from .criterions import RoiMeanLoss, WithRoiMean  # noqa: F401
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
 def __getattr__(name):

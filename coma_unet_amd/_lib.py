@@ -104,6 +104,10 @@ SIGNATURES = {
     "coma_roi_wloss_ws_bytes": (_sz, [_TP]),
     "coma_roi_wloss_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "coma_roi_wloss_bwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _f32, _vp, _vp, _TP, _vp]),
+    "coma_roi_mean_ws_bytes": (_sz, [_TP]),
+    "coma_roi_mean_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "coma_roi_mean_bwd": (_i32, [_TP, _vp, _i32, _vp, _vp, _TP, _vp]),
+    "coma_roi_region_stats": (_i32, [_TP, _TP, _TP, _vp, _i32, _vp, _vp, _sz, _vp]),
     "coma_eval_stats": (_i32, [_TP, _TP, _TP, _vp, _i32, _vp, _vp]),
     "coma_ssim_ws_bytes": (_sz, [_TP, _i32]),
     "coma_ssim_partial": (_i32, [_TP, _TP, _vp, _i32, _f32, _f32, _vp, _sz, _vp, _vp]),

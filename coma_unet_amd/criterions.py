@@ -3,7 +3,8 @@
 Same class names / call signatures as /root/reference/criterions.py:
 ``RoiMSE`` (:124-211), ``GenerativeContrastiveLoss`` (:485-575),
 ``LabelDifference`` / ``FeatureSimilarity`` / ``RnCLoss`` (:579-644), and the two voxel-weighted alternatives the
-drivers keep at hand, ``RoiRRMSE`` / ``RoiRSE`` (:28-122), with ``RoiWeightedMSE`` beside them.  The voxel losses are
+drivers keep at hand, ``RoiRRMSE`` / ``RoiRSE`` (:28-122), with ``RoiWeightedMSE`` beside them, and ``RoiMeanLoss`` /
+``WithRoiMean``, a loss on the regional means the validation loop reports (no counterpart upstream).  The voxel losses are
 fused HIP kernels (one pass: label->weight LUT, squared/absolute difference, per-sample
 reduction; gradient in one more pass).  RnC works on a (B, 512) feature matrix and a (B, 6)
 label matrix -- a few thousand numbers -- and stays as torch glue.
@@ -295,6 +296,114 @@ class WithSSIM(nn.Module):
         return loss + self.ssim_weight * (s if self.batch_reduction is None else torch.mean(s))
 
 
+class RoiMeanLoss(_RoiTables, nn.Module):
+    """A loss on the regional means (the per-ROI SUVR means the validation loop reports): per sample, with
+    d_r = mean_r(pred) - mean_r(gt) over the voxels labelled roi_indices[r],
+        loss_b = sum_r w_r phi(d_r) / sum_r w_r     over the regions PRESENT in the sample's label volume
+    phi = d^2 (kind "mse"), |d| ("l1") or huber_loss's pointwise form with `delta` ("huber").  A region without voxels is
+    skipped; a sample with no present region (or zero total weight) has loss 0 and gradient 0 -- never NaN.  Labels follow
+    the kernels' table rules: exact integer values, the first occurrence of a duplicated id wins.  One fused label-segmented
+    reduction without atomics (csrc/roi_mean.hip, bitwise repeatable) and one streaming backward; the target gets no gradient.
+
+    `reduction` ("mean", "sum" or None: the per-sample (B, 1) vector) is also readable and writable as `batch_reduction`."""
+
+    KINDS = ops.RoiMeanLoss.KINDS
+
+    def __init__(self, roi_weights, roi_indices, kind="mse", delta=1.0, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum", None):
+            raise ValueError(f"RoiMeanLoss: reduction must be 'mean', 'sum' or None, got {reduction!r}")
+        if kind not in self.KINDS:
+            raise ValueError(f"RoiMeanLoss: kind must be one of {sorted(self.KINDS)}, got {kind!r}")
+        n = len(roi_indices)
+        if not 1 <= n <= 64:
+            raise ValueError(f"RoiMeanLoss: 1..64 ROI indices expected, got {n}")
+        if len(roi_weights) != n:
+            raise ValueError(f"RoiMeanLoss: {len(roi_weights)} weights for {n} ROI indices")
+        d = float(delta)
+        if kind == "huber" and not (d > 0.0 and d != float("inf")):
+            raise ValueError(f"RoiMeanLoss: huber delta must be positive and finite, got {delta}")
+        self.roi_weights = roi_weights
+        self.roi_indices = roi_indices
+        self.kind = kind
+        self.delta = d
+        self.batch_reduction = reduction
+
+    @property
+    def reduction(self):
+        return self.batch_reduction
+
+    @reduction.setter
+    def reduction(self, value):
+        self.batch_reduction = value
+
+    def __str__(self):
+        return (f"RoiMeanLoss(\n  roi_weights={self.roi_weights}\n  roi_indices={self.roi_indices}\n  kind={self.kind}\n"
+                f"  reduction={self.batch_reduction}\n)")
+
+    def forward(self, pred, gt, roi):
+        if roi is None:
+            raise ValueError("RoiMeanLoss: needs the ROI label volume")
+        if pred.dim() != 5 or pred.shape[1] != 1 or pred.shape != gt.shape or pred.shape != roi.shape:
+            raise ValueError(f"RoiMeanLoss: (B, 1, D, H, W) volumes of equal shape expected, got {tuple(pred.shape)}, "
+                             f"{tuple(gt.shape)}, {tuple(roi.shape)}")
+        ids, w = self._tables(pred.device)
+        p = _vol_internal(pred)
+        loss = ops.RoiMeanLoss.apply(p, _vol_internal(gt.detach(), p.dtype).contiguous(),
+                                     _vol_internal(roi, torch.float32).contiguous(), ids, w,
+                                     self.KINDS[self.kind], self.delta)   # (B, 1)
+        if self.batch_reduction is None:
+            return loss
+        return torch.mean(loss) if self.batch_reduction == "mean" else torch.sum(loss)
+
+
+class WithRoiMean(nn.Module):
+    """A generative loss plus a regional-mean term: base(pred, gt, roi) + roi_mean_weight * roi_mean_b (RoiMeanLoss) -- per
+    sample while `batch_reduction` is None, else reduced over the batch as the base is.  `batch_reduction` IS the base
+    loss's, and so is everything else WithSSIM forwards; the two wrappers nest in either order.  The term's tables are
+    `roi_weights` / `roi_indices` when given, else the base's LIVE ones: a weight update of the base reaches the term."""
+
+    _BASE_ATTRS = WithSSIM._BASE_ATTRS
+    _BASE_METHODS = WithSSIM._BASE_METHODS
+
+    def __init__(self, base, roi_mean_weight, kind="mse", delta=1.0, roi_weights=None, roi_indices=None):
+        super().__init__()
+        if not hasattr(base, "batch_reduction"):
+            raise ValueError("WithRoiMean: base must be a generative loss with a batch_reduction attribute")
+        w = float(roi_mean_weight)
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError(f"WithRoiMean: roi_mean_weight must be a finite number >= 0, got {roi_mean_weight}")
+        if (roi_weights is None) != (roi_indices is None):
+            raise ValueError("WithRoiMean: give both roi_weights and roi_indices, or neither (the base's tables)")
+        live = roi_weights is None
+        if live and not (hasattr(base, "roi_weights") and hasattr(base, "roi_indices")):
+            raise ValueError("WithRoiMean: base has no ROI tables: pass roi_weights and roi_indices")
+        self.base = base
+        self.roi_mean_weight = w
+        self.live_tables = live
+        self.roi_mean = RoiMeanLoss(base.roi_weights if live else roi_weights, base.roi_indices if live else roi_indices,
+                                    kind=kind, delta=delta, reduction=None)
+
+    def __getattr__(self, name):
+        if name in WithRoiMean._BASE_ATTRS or name in WithRoiMean._BASE_METHODS:
+            return getattr(super().__getattr__("base"), name)
+        return super().__getattr__(name)
+
+    def __setattr__(self, name, value):
+        if name in WithRoiMean._BASE_ATTRS:
+            setattr(self.base, name, value)
+        else:
+            super().__setattr__(name, value)
+
+    def forward(self, pred, gt, roi=None):
+        loss = self.base(pred, gt, roi)
+        if self.live_tables:
+            self.roi_mean.roi_weights, self.roi_mean.roi_indices = self.base.roi_weights, self.base.roi_indices
+        m = self.roi_mean(pred, gt, roi)                           # (B, 1)
+        red = self.batch_reduction
+        return loss + self.roi_mean_weight * (m if red is None else torch.mean(m) if red == "mean" else torch.sum(m))
+
+
 class LabelDifference(nn.Module):
     def __init__(self, distance_type="l1"):
         super().__init__()
@@ -419,14 +528,16 @@ GEN_LOSSES = {"roi_mse": lambda w: RoiMSE(w, ROI_INDICES, voxel_wise=False), "ro
               "roi_rrmse": lambda w: RoiRRMSE(w, ROI_INDICES), "roi_wmse": lambda w: RoiWeightedMSE(w, ROI_INDICES)}
 
 
-def build_reference_criterion(device="cuda", gen_loss="roi_mse"):
+def build_reference_criterion(device="cuda", gen_loss="roi_mse", roi_mean_weight=None):
     """validation.py:130-154 with ``-rnc`` + attn_unet_data_parallel.py:717.  `gen_loss`: "roi_mse" (the live driver line,
     validation.py:146) or one of the alternatives the reference keeps beside it (:132-133), "roi_rse" / "roi_rrmse", or
-    "roi_wmse"."""
+    "roi_wmse".  `roi_mean_weight` (None: as the reference): the generative loss wrapped in WithRoiMean with that weight."""
     if gen_loss not in GEN_LOSSES:
         raise ValueError(f"build_reference_criterion: gen_loss must be one of {sorted(GEN_LOSSES)}, got {gen_loss!r}")
     w = torch.full((len(ROI_INDICES),), 225.0, device=device)
     crit = GenerativeContrastiveLoss(RnCLoss(), GEN_LOSSES[gen_loss](w),
                                      nn.TripletMarginLoss(1), regulatory_weight=0.0, ds_regulatory_weight=1.0)
     crit.gen_loss.batch_reduction = None
+    if roi_mean_weight is not None:
+        crit.gen_loss = WithRoiMean(crit.gen_loss, roi_mean_weight)
     return crit

@@ -1499,6 +1499,49 @@ class RoiWeightedLoss(Function):
         return dpred, None, None, None, None, None, None
 
 
+class RoiMeanLoss(Function):
+    """The ROI-mean loss of csrc/roi_mean.hip (DESIGN.md section 4 "ROI-mean loss"): per-sample loss vector (B, 1) on the
+    differences of the regional means of `pred` and `gt`, kind 0 squared, 1 absolute, 2 huber with `delta`.  Saved: the
+    labels, the id table and `coef` (B x n_roi floats) -- neither `pred` nor `gt`: the gradient of a voxel is its region's
+    coefficient.  The target gets no gradient."""
+
+    MSE, L1, HUBER = 0, 1, 2
+    KINDS = {"mse": MSE, "l1": L1, "huber": HUBER}
+
+    @staticmethod
+    def forward(ctx, pred, gt, roi, roi_ids, roi_w, kind, delta):
+        B, n = pred.shape[0], roi_ids.numel()
+        cp = ct(pred)
+        loss, coef = _f32(B, pred.device), _f32((B, n), pred.device)
+        ws = workspace(lib.coma_roi_mean_ws_bytes(cp), pred.device)
+        check(lib.coma_roi_mean_fwd(cp, ct(gt), ct(roi), ptr(roi_ids), ptr(roi_w), n, int(kind), float(delta),
+                                    ptr(loss), ptr(coef), ptr(ws), ws.numel(), L.stream()), "coma_roi_mean_fwd")
+        ctx.save_for_backward(roi, roi_ids, coef)
+        ctx.meta = (pred.shape, pred.dtype)
+        return loss.view(B, 1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        roi, roi_ids, coef = ctx.saved_tensors
+        g = gout.contiguous().float().view(-1)
+        dpred = torch.empty(ctx.meta[0], dtype=ctx.meta[1], device=roi.device)       # dense: the 16-byte store path
+        check(lib.coma_roi_mean_bwd(ct(roi), ptr(roi_ids), roi_ids.numel(), ptr(g), ptr(coef), ct(dpred), L.stream()),
+              "coma_roi_mean_bwd")
+        return dpred, None, None, None, None, None, None
+
+
+def roi_region_stats(pred, gt, roi, roi_ids):
+    """(B, D, H, W, 1) pred / gt (fp32 or bf16) and fp32 labels, int32 device id table -> fp64 (B, n_roi, 3) of
+    {voxel count, sum pred, sum gt} per region, by the ROI-mean loss's fixed-order reduction (bitwise repeatable)."""
+    cp = ct(pred)
+    n = roi_ids.numel()
+    stats = torch.empty((pred.shape[0], n, 3), dtype=torch.float64, device=pred.device)
+    ws = workspace(lib.coma_roi_mean_ws_bytes(cp), pred.device)
+    check(lib.coma_roi_region_stats(cp, ct(gt), ct(roi), ptr(roi_ids), n, ptr(stats), ptr(ws), ws.numel(), L.stream()),
+          "coma_roi_region_stats")
+    return stats
+
+
 class L1Loss(Function):
     """Per-sample voxel MAE (the reference's evaluation metric, attn_unet_data_parallel.py:1215)."""
 

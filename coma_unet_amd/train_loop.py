@@ -106,6 +106,26 @@ def with_ssim(criterion, ssim_weight=None, ssim_kwargs=None):
     return criterion
 
 
+def with_roi_mean(criterion, roi_mean_weight=None, roi_mean_kwargs=None):
+    """train_dp's ``roi_mean_weight`` option: wrap ``criterion.gen_loss`` in criterions.WithRoiMean -- once: a loss that
+    already carries the term (directly, or under a WithSSIM wrapper) only takes the new weight.  None: nothing is touched.
+    The term goes BELOW a WithSSIM wrapper (train_dp applies it before with_ssim), so that with_ssim keeps finding its own
+    wrapper on top on a later call."""
+    if roi_mean_weight is None:
+        return criterion
+    from .criterions import WithRoiMean, WithSSIM
+    g = criterion.gen_loss
+    while g is not None and not isinstance(g, WithRoiMean):
+        g = getattr(g, "base", None)
+    if g is not None:
+        g.roi_mean_weight = float(roi_mean_weight)
+    elif isinstance(criterion.gen_loss, WithSSIM):
+        criterion.gen_loss.base = WithRoiMean(criterion.gen_loss.base, roi_mean_weight, **(roi_mean_kwargs or {}))
+    else:
+        criterion.gen_loss = WithRoiMean(criterion.gen_loss, roi_mean_weight, **(roi_mean_kwargs or {}))
+    return criterion
+
+
 def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save_path="", cuda_id=0, pred_sample_file="",
              from_checkpoint=False, **kwargs):
     """attn_unet_data_parallel.py:696.  Returns the list of per-epoch average losses (the reference returns None; the
@@ -146,6 +166,10 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        ``criterions.WithSSIM(gen_loss, ssim_weight, **ssim_kwargs)`` -- every sample's generative loss gains
        ``ssim_weight * (1 - SSIM_b)``, computed and differentiated by the fused SSIM kernels; the ROI tables and weight
        updates stay the wrapped loss's.  With None the criterion is not touched and no SSIM kernel runs.
+     * ``roi_mean_weight`` / ``roi_mean_kwargs`` (None): with a weight, ``criterion.gen_loss`` is wrapped once in
+       ``criterions.WithRoiMean(gen_loss, roi_mean_weight, **roi_mean_kwargs)`` -- every sample's generative loss gains
+       ``roi_mean_weight`` times the loss on its regional (per-ROI) means, by the fused segmented reduction; the term
+       follows the wrapped loss's live ROI weights.  With None the criterion is not touched and no such kernel runs.
      * ``augment`` (None | augment.Augment3D | dict of its arguments): on-device augmentation of every TRAINING batch -- one
        fused kernel warps mri / tau / roi by the same random per-sample transform right after the batch reached the device,
        before the graph load or the eager step (the augmented batch has the captured shapes, so the graph path is as
@@ -163,6 +187,7 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     import torch.distributed as dist
     if "freeze_bn" in kwargs:
         model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
+    with_roi_mean(criterion, kwargs.get("roi_mean_weight"), kwargs.get("roi_mean_kwargs"))
     with_ssim(criterion, kwargs.get("ssim_weight"), kwargs.get("ssim_kwargs"))
     augment = kwargs.get("augment")
     kwargs["smooth_tau"] = _smoother(kwargs.get("smooth_tau"))      # (built once; contrastive_test gets the instance)

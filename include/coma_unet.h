@@ -418,6 +418,24 @@ int coma_roi_wloss_bwd(const coma_tensor* pred, const coma_tensor* gt, const com
                        const int32_t* roi_ids, const float* roi_w, int32_t n_roi, float bg_weight,
                        const float* gout, const float* coef, const coma_tensor* dpred, void* stream);
 
+/* ---- ROI-mean (per-region SUVR) loss (csrc/roi_mean.hip): a loss on the regional means.  Per sample and table slot r,
+ * n_r = #{v: label_v == roi_ids[r]} (roi_lut_slot's rules: exact integer labels, the first of a duplicated id wins),
+ * d_r = mean_r(pred) - mean_r(gt);
+ *   loss = sum_{r: n_r > 0} w_r phi(d_r) / sum_{r: n_r > 0} w_r,   phi: kind 0 d^2 | kind 1 |d| | kind 2 huber(d; delta)
+ *   coef[b][r] = w_r phi'(d_r) / (n_r sum w)    (0 for an absent region; phi'(0) = 0 for kind 1)
+ * No present region, or sum w = 0: loss 0 and coef 0.  loss: B floats; coef: B x n_roi floats.  pred / gt: one dtype (fp32
+ * or bf16), C = 1; gt and roi (fp32) of voxel pitch 1.  A label-segmented reduction without atomics: bitwise repeatable. */
+size_t coma_roi_mean_ws_bytes(const coma_tensor* pred);
+int coma_roi_mean_fwd(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi,
+                      const int32_t* roi_ids, const float* roi_w, int32_t n_roi, int32_t kind, float delta,
+                      float* loss, float* coef, void* ws, size_t ws_bytes, void* stream);
+/* dpred (=) gout[b] * coef[b][slot of the voxel's label], 0 for a voxel in no region; dpred fp32 or bf16, any voxel pitch */
+int coma_roi_mean_bwd(const coma_tensor* roi, const int32_t* roi_ids, int32_t n_roi, const float* gout, const float* coef,
+                      const coma_tensor* dpred, void* stream);
+/* stats: fp64 [B][n_roi][3] = {n_r, sum_r pred, sum_r gt}, by the same reduction (ws: coma_roi_mean_ws_bytes) */
+int coma_roi_region_stats(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi,
+                          const int32_t* roi_ids, int32_t n_roi, double* stats, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- evaluation statistics: one pass over (pred, gt, roi) giving, per sample and per
  *      bin (n_roi ROIs + the whole volume), the sums behind calc_roi_metrics (attn_unet_data_parallel.py:1361-1397),
  *      the global MAE/MAPE/RSE/RRMSE of contrastive_test (:1214-1231) and RoiCorrMetric (:49-60).
