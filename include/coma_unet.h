@@ -232,6 +232,12 @@ size_t coma_conv_wgrad_ws_bytes(const coma_conv_desc* d, const coma_tensor* x, c
 /* the part of it that must be ZERO for the kernels' atomic merges (0 = none): with COMA_ZEROED_WS and dbias == NULL a
  * caller may pass a private pre-zeroed buffer of just this size as `ws`                                          */
 size_t coma_conv_wgrad_zs_bytes(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy);
+/* What coma_conv_wgrad does with `ws` follows from ws_bytes alone (tests/test_conv_ws_gpu.py): with dbias != NULL it needs
+ * ws_bytes >= coma_norm_ws_bytes(dy) -- less is an error and nothing is written -- writes the bias gradient's partial rows
+ * there first and then ignores COMA_ZEROED_WS; the blocks merge into replicas in the first coma_conv_wgrad_zs_bytes() bytes
+ * only when that is non-zero and ws_bytes is at least as large, otherwise (a smaller or NULL ws) into dwk itself.
+ * COMA_ZEROED_WS speaks about the replica bytes, COMA_ZEROED_OUT about dwk: each spares the memset of the branch that
+ * merges there.  Nothing beyond the bytes named here is touched.                                                      */
 int coma_conv_wgrad(const coma_conv_desc* d, const coma_tensor* x, const coma_tensor* dy,
                     float* dwk, float* dbias, void* ws, size_t ws_bytes, int32_t zeroed, void* stream);
 
