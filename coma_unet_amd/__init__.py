@@ -10,6 +10,7 @@ from .inference import Predictor, fold_gate
 from .optim import FusedAdamW, LRSchedule
 from .criterions import RoiRSE, RoiRRMSE, RoiWeightedMSE  # noqa: F401
 from .criterions import RoiMeanLoss, WithRoiMean  # noqa: F401
+from .criterions import GradientDifferenceLoss, WithGradDiff  # noqa: F401
 from .criterions import RoiMSE, RnCLoss, GenerativeContrastiveLoss, VoxelL1, SSIMLoss, WithSSIM, build_reference_criterion
 
 def __getattr__(name):

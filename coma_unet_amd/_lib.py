@@ -108,6 +108,9 @@ SIGNATURES = {
     "coma_roi_mean_fwd": (_i32, [_TP, _TP, _TP, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "coma_roi_mean_bwd": (_i32, [_TP, _vp, _i32, _vp, _vp, _TP, _vp]),
     "coma_roi_region_stats": (_i32, [_TP, _TP, _TP, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "coma_grad_diff_ws_bytes": (_sz, [_TP]),
+    "coma_grad_diff_fwd": (_i32, [_TP, _TP, _TP, _i32, _i32, C.POINTER(_f32), _vp, _vp, _vp, _sz, _vp]),
+    "coma_grad_diff_bwd": (_i32, [_TP, _TP, _TP, _i32, _i32, _vp, _vp, _TP, _vp]),
     "coma_eval_stats": (_i32, [_TP, _TP, _TP, _vp, _i32, _vp, _vp]),
     "coma_ssim_ws_bytes": (_sz, [_TP, _i32]),
     "coma_ssim_partial": (_i32, [_TP, _TP, _vp, _i32, _f32, _f32, _vp, _sz, _vp, _vp]),

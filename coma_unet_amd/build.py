@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcoma_unet.so")
 # (the two slowest to compile first)
 SOURCES = ["conv_wgrad.hip", "conv_mfma.hip", "conv_tconv.hip", "conv_duo.hip", "api.hip", "conv_direct.hip", "conv_point1.hip", "conv_split.hip",
-           "conv_pw_f32.hip", "norm.hip", "gate.hip", "elementwise.hip", "roi_loss.hip", "roi_mean.hip", "weights.hip", "metrics.hip", "augment.hip", "smooth.hip", "comm.hip"]
+           "conv_pw_f32.hip", "norm.hip", "gate.hip", "elementwise.hip", "roi_loss.hip", "roi_mean.hip", "grad_diff.hip", "weights.hip", "metrics.hip", "augment.hip", "smooth.hip", "comm.hip"]
 MAX_PROCS = 16      # compiler processes at a time
 
 

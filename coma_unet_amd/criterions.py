@@ -4,7 +4,8 @@ Same class names / call signatures as /root/reference/criterions.py:
 ``RoiMSE`` (:124-211), ``GenerativeContrastiveLoss`` (:485-575),
 ``LabelDifference`` / ``FeatureSimilarity`` / ``RnCLoss`` (:579-644), and the two voxel-weighted alternatives the
 drivers keep at hand, ``RoiRRMSE`` / ``RoiRSE`` (:28-122), with ``RoiWeightedMSE`` beside them, and ``RoiMeanLoss`` /
-``WithRoiMean``, a loss on the regional means the validation loop reports (no counterpart upstream).  The voxel losses are
+``WithRoiMean``, a loss on the regional means the validation loop reports, and ``GradientDifferenceLoss`` / ``WithGradDiff``,
+an edge term on the image gradient (neither has a counterpart upstream).  The voxel losses are
 fused HIP kernels (one pass: label->weight LUT, squared/absolute difference, per-sample
 reduction; gradient in one more pass).  RnC works on a (B, 512) feature matrix and a (B, 6)
 label matrix -- a few thousand numbers -- and stays as torch glue.
@@ -404,6 +405,114 @@ class WithRoiMean(nn.Module):
         return loss + self.roi_mean_weight * (m if red is None else torch.mean(m) if red == "mean" else torch.sum(m))
 
 
+class GradientDifferenceLoss(nn.Module):
+    """Gradient-difference loss (Mathieu et al. 2016; Nie et al. 2018): the edge term that counters the blur of a squared-error
+    loss.  Per sample, with gp / gg the forward differences of pred / gt along axis a in (z, y, x),
+        loss_b = sum_a axis_weights[a] * mean over the counted pairs of | |gp| - |gg| |^alpha    (mode "abs", the classic form)
+                                                                     or |  gp  -  gg  |^alpha    (mode "signed")
+    alpha 1 or 2.  mask None counts every pair; mask "brain" only those whose two voxels both have a non-zero label in `roi`
+    (the MRI is zeroed outside the label volume: the brain boundary is no edge to learn).  An axis of length 1 or without a
+    counted pair contributes 0 -- never NaN; sign(0) = 0 in the gradient, torch's subgradient of abs.  One fused tile pass
+    forward and one backward (csrc/grad_diff.hip), no atomics, bitwise repeatable; the target gets no gradient.  For physical
+    gradients on anisotropic voxels pass axis_weights = (1 / spacing_a) ** alpha.
+
+    `reduction` ("mean", "sum" or None: the per-sample (B, 1) vector) is also readable and writable as `batch_reduction`."""
+
+    MODES = ops.GradDiffLoss.MODES
+
+    def __init__(self, alpha=1, mode="abs", axis_weights=(1.0, 1.0, 1.0), mask=None, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum", None):
+            raise ValueError(f"GradientDifferenceLoss: reduction must be 'mean', 'sum' or None, got {reduction!r}")
+        if isinstance(alpha, bool) or alpha not in (1, 2):
+            raise ValueError(f"GradientDifferenceLoss: alpha must be 1 or 2, got {alpha!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"GradientDifferenceLoss: mode must be one of {sorted(self.MODES)}, got {mode!r}")
+        if mask not in (None, "brain"):
+            raise ValueError(f"GradientDifferenceLoss: mask must be None or 'brain', got {mask!r}")
+        try:
+            aw = tuple(float(a) for a in axis_weights)
+        except TypeError:
+            aw = ()
+        if len(aw) != 3 or not all(a >= 0.0 and a != float("inf") for a in aw):
+            raise ValueError(f"GradientDifferenceLoss: axis_weights must be three finite numbers >= 0 (z, y, x), got {axis_weights!r}")
+        self.alpha = int(alpha)
+        self.mode = mode
+        self.axis_weights = aw
+        self.mask = mask
+        self.batch_reduction = reduction
+
+    @property
+    def reduction(self):
+        return self.batch_reduction
+
+    @reduction.setter
+    def reduction(self, value):
+        self.batch_reduction = value
+
+    def __str__(self):
+        return (f"GradientDifferenceLoss(\n  alpha={self.alpha}\n  mode={self.mode}\n  axis_weights={self.axis_weights}\n"
+                f"  mask={self.mask}\n  reduction={self.batch_reduction}\n)")
+
+    def per_sample(self, pred, gt, roi=None, differentiable=True):
+        """The (B, 1) per-sample values; `differentiable=False`: the forward kernel alone, nothing saved."""
+        if pred.dim() != 5 or pred.shape[1] != 1 or pred.shape != gt.shape or (roi is not None and roi.shape != pred.shape):
+            raise ValueError(f"GradientDifferenceLoss: (B, 1, D, H, W) volumes of equal shape expected, got {tuple(pred.shape)}, "
+                             f"{tuple(gt.shape)}" + ("" if roi is None else f", {tuple(roi.shape)}"))
+        if self.mask == "brain" and roi is None:
+            raise ValueError("GradientDifferenceLoss: mask='brain' needs the ROI label volume")
+        p = _vol_internal(pred)
+        g = _vol_internal(gt.detach(), p.dtype).contiguous()
+        r = _vol_internal(roi, torch.float32).contiguous() if self.mask == "brain" else None
+        if differentiable:
+            return ops.GradDiffLoss.apply(p, g, r, self.MODES[self.mode], self.alpha, self.axis_weights)
+        return ops.grad_diff_values(p.detach(), g, r, self.MODES[self.mode], self.alpha, self.axis_weights).view(-1, 1)
+
+    def forward(self, pred, gt, roi=None):
+        loss = self.per_sample(pred, gt, roi)                      # (B, 1)
+        if self.batch_reduction is None:
+            return loss
+        return torch.mean(loss) if self.batch_reduction == "mean" else torch.sum(loss)
+
+
+class WithGradDiff(nn.Module):
+    """A generative loss plus a gradient-difference term: base(pred, gt, roi) + grad_diff_weight * gdl_b
+    (GradientDifferenceLoss(**kwargs)) -- per sample while `batch_reduction` is None, else reduced over the batch as the base
+    is.  `batch_reduction` IS the base loss's, and so is everything else WithSSIM forwards; nests with WithSSIM and
+    WithRoiMean in any order."""
+
+    _BASE_ATTRS = WithSSIM._BASE_ATTRS
+    _BASE_METHODS = WithSSIM._BASE_METHODS
+
+    def __init__(self, base, grad_diff_weight, **kwargs):
+        super().__init__()
+        if not hasattr(base, "batch_reduction"):
+            raise ValueError("WithGradDiff: base must be a generative loss with a batch_reduction attribute")
+        w = float(grad_diff_weight)
+        if not (w >= 0.0 and w != float("inf")):
+            raise ValueError(f"WithGradDiff: grad_diff_weight must be a finite number >= 0, got {grad_diff_weight}")
+        self.base = base
+        self.grad_diff_weight = w
+        self.grad_diff = GradientDifferenceLoss(**dict(kwargs, reduction=None))
+
+    def __getattr__(self, name):
+        if name in WithGradDiff._BASE_ATTRS or name in WithGradDiff._BASE_METHODS:
+            return getattr(super().__getattr__("base"), name)
+        return super().__getattr__(name)
+
+    def __setattr__(self, name, value):
+        if name in WithGradDiff._BASE_ATTRS:
+            setattr(self.base, name, value)
+        else:
+            super().__setattr__(name, value)
+
+    def forward(self, pred, gt, roi=None):
+        loss = self.base(pred, gt, roi)
+        g = self.grad_diff(pred, gt, roi)                          # (B, 1)
+        red = self.batch_reduction
+        return loss + self.grad_diff_weight * (g if red is None else torch.mean(g) if red == "mean" else torch.sum(g))
+
+
 class LabelDifference(nn.Module):
     def __init__(self, distance_type="l1"):
         super().__init__()
@@ -528,10 +637,11 @@ GEN_LOSSES = {"roi_mse": lambda w: RoiMSE(w, ROI_INDICES, voxel_wise=False), "ro
               "roi_rrmse": lambda w: RoiRRMSE(w, ROI_INDICES), "roi_wmse": lambda w: RoiWeightedMSE(w, ROI_INDICES)}
 
 
-def build_reference_criterion(device="cuda", gen_loss="roi_mse", roi_mean_weight=None):
+def build_reference_criterion(device="cuda", gen_loss="roi_mse", roi_mean_weight=None, grad_diff_weight=None):
     """validation.py:130-154 with ``-rnc`` + attn_unet_data_parallel.py:717.  `gen_loss`: "roi_mse" (the live driver line,
     validation.py:146) or one of the alternatives the reference keeps beside it (:132-133), "roi_rse" / "roi_rrmse", or
-    "roi_wmse".  `roi_mean_weight` (None: as the reference): the generative loss wrapped in WithRoiMean with that weight."""
+    "roi_wmse".  `roi_mean_weight` (None: as the reference): the generative loss wrapped in WithRoiMean with that weight;
+    `grad_diff_weight` (None: as the reference): wrapped in WithGradDiff with that weight (the classic term: alpha 1, "abs")."""
     if gen_loss not in GEN_LOSSES:
         raise ValueError(f"build_reference_criterion: gen_loss must be one of {sorted(GEN_LOSSES)}, got {gen_loss!r}")
     w = torch.full((len(ROI_INDICES),), 225.0, device=device)
@@ -540,4 +650,6 @@ def build_reference_criterion(device="cuda", gen_loss="roi_mse", roi_mean_weight
     crit.gen_loss.batch_reduction = None
     if roi_mean_weight is not None:
         crit.gen_loss = WithRoiMean(crit.gen_loss, roi_mean_weight)
+    if grad_diff_weight is not None:
+        crit.gen_loss = WithGradDiff(crit.gen_loss, grad_diff_weight)
     return crit

@@ -126,6 +126,15 @@ def ssim3d(y_pred, y, data_range=1.0, kernel_type="gaussian", win_size=11, kerne
     return part.view(B, nt.value).sum(1) / nvalid
 
 
+def gradient_difference(pred, gt, roi=None, **kwargs):
+    """Per-sample gradient-difference values (B,) fp32 of (B, 1, D, H, W) volumes -- a sharpness figure to log: the value of
+    criterions.GradientDifferenceLoss(**kwargs) (alpha, mode, axis_weights, mask) from its forward kernel alone; nothing is
+    saved for a backward.  Not part of contrastive_test's outputs."""
+    from .criterions import GradientDifferenceLoss
+    crit = GradientDifferenceLoss(**dict(kwargs, reduction=None))
+    return crit.per_sample(pred.detach(), gt, roi, differentiable=False).reshape(-1)
+
+
 class SSIMMetric:
     """MONAI's cumulative metric surface as the reference uses it: `m(y_pred=..., y=...)` per batch, `aggregate()`,
     `reset()` (:1234,1300-1301)."""

@@ -1542,6 +1542,49 @@ def roi_region_stats(pred, gt, roi, roi_ids):
     return stats
 
 
+def _grad_diff_fwd(pred, gt, roi, mode, alpha, axis_w):
+    """-> loss (B,), coef (B, 3) of coma_grad_diff_fwd; roi None: no mask"""
+    B = pred.shape[0]
+    cp = ct(pred)
+    loss, coef = _f32(B, pred.device), _f32((B, 3), pred.device)
+    ws = workspace(lib.coma_grad_diff_ws_bytes(cp), pred.device)
+    aw = (ctypes.c_float * 3)(*[float(a) for a in axis_w])
+    check(lib.coma_grad_diff_fwd(cp, ct(gt), None if roi is None else ct(roi), int(mode), int(alpha), aw, ptr(loss), ptr(coef),
+                                 ptr(ws), ws.numel(), L.stream()), "coma_grad_diff_fwd")
+    return loss, coef
+
+
+class GradDiffLoss(Function):
+    """The gradient-difference loss of csrc/grad_diff.hip (DESIGN.md section 4 "Gradient-difference loss"): per-sample loss
+    vector (B, 1) on the forward differences of `pred` and `gt` along z, y, x; mode 0 "abs" (| |gp| - |gg| |^alpha) or 1
+    "signed" (|gp - gg|^alpha), alpha 1 or 2, `axis_w` three host floats, `roi` None or the label volume whose zeros mask
+    pairs out.  Saved: pred, gt, roi and `coef` (B x 3 floats).  The target gets no gradient."""
+
+    ABS, SIGNED = 0, 1
+    MODES = {"abs": ABS, "signed": SIGNED}
+
+    @staticmethod
+    def forward(ctx, pred, gt, roi, mode, alpha, axis_w):
+        loss, coef = _grad_diff_fwd(pred, gt, roi, mode, alpha, axis_w)
+        ctx.save_for_backward(pred, gt, roi, coef)
+        ctx.cfg = (int(mode), int(alpha))
+        return loss.view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, roi, coef = ctx.saved_tensors
+        g = gout.contiguous().float().view(-1)
+        dpred = torch.empty_like(pred)
+        check(lib.coma_grad_diff_bwd(ct(pred), ct(gt), None if roi is None else ct(roi), ctx.cfg[0], ctx.cfg[1], ptr(g), ptr(coef),
+                                     ct(dpred), L.stream()), "coma_grad_diff_bwd")
+        return dpred, None, None, None, None, None
+
+
+def grad_diff_values(pred, gt, roi=None, mode=0, alpha=1, axis_w=(1.0, 1.0, 1.0)):
+    """(B, D, H, W, 1) volumes -> the per-sample (B,) gradient-difference values, by the forward kernel alone."""
+    return _grad_diff_fwd(pred, gt, roi, mode, alpha, axis_w)[0]
+
+
 class L1Loss(Function):
     """Per-sample voxel MAE (the reference's evaluation metric, attn_unet_data_parallel.py:1215)."""
 

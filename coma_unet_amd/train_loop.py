@@ -126,6 +126,31 @@ def with_roi_mean(criterion, roi_mean_weight=None, roi_mean_kwargs=None):
     return criterion
 
 
+def with_grad_diff(criterion, grad_diff_weight=None, grad_diff_kwargs=None):
+    """train_dp's ``grad_diff_weight`` option: wrap ``criterion.gen_loss`` in criterions.WithGradDiff -- once: a loss that
+    already carries the term anywhere in its chain of wrappers only takes the new weight.  None: nothing is touched.  The
+    term goes BELOW any WithSSIM / WithRoiMean wrapper, directly around the base loss, so that with_ssim and with_roi_mean
+    keep finding their own wrappers where they put them."""
+    if grad_diff_weight is None:
+        return criterion
+    from .criterions import WithGradDiff, WithRoiMean, WithSSIM
+    g = criterion.gen_loss
+    while g is not None and not isinstance(g, WithGradDiff):
+        g = getattr(g, "base", None)
+    if g is not None:
+        g.grad_diff_weight = float(grad_diff_weight)
+        return criterion
+    parent, g = None, criterion.gen_loss
+    while isinstance(g, (WithSSIM, WithRoiMean)):
+        parent, g = g, g.base
+    wrapped = WithGradDiff(g, grad_diff_weight, **(grad_diff_kwargs or {}))
+    if parent is None:
+        criterion.gen_loss = wrapped
+    else:
+        parent.base = wrapped
+    return criterion
+
+
 def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save_path="", cuda_id=0, pred_sample_file="",
              from_checkpoint=False, **kwargs):
     """attn_unet_data_parallel.py:696.  Returns the list of per-epoch average losses (the reference returns None; the
@@ -170,6 +195,11 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
        ``criterions.WithRoiMean(gen_loss, roi_mean_weight, **roi_mean_kwargs)`` -- every sample's generative loss gains
        ``roi_mean_weight`` times the loss on its regional (per-ROI) means, by the fused segmented reduction; the term
        follows the wrapped loss's live ROI weights.  With None the criterion is not touched and no such kernel runs.
+     * ``grad_diff_weight`` / ``grad_diff_kwargs`` (None): with a weight, ``criterion.gen_loss`` is wrapped once in
+       ``criterions.WithGradDiff(gen_loss, grad_diff_weight, **grad_diff_kwargs)`` -- every sample's generative loss gains
+       ``grad_diff_weight`` times its gradient-difference loss (``alpha``, ``mode``, ``axis_weights``, ``mask`` as
+       ``criterions.GradientDifferenceLoss``), one fused tile pass forward and one backward on the prediction.  With None the
+       criterion is not touched, nothing is allocated and no such kernel runs.
      * ``augment`` (None | augment.Augment3D | dict of its arguments): on-device augmentation of every TRAINING batch -- one
        fused kernel warps mri / tau / roi by the same random per-sample transform right after the batch reached the device,
        before the graph load or the eager step (the augmented batch has the captured shapes, so the graph path is as
@@ -187,6 +217,7 @@ def train_dp(model, criterion, train_loader, validation_loader, epochs, lr, save
     import torch.distributed as dist
     if "freeze_bn" in kwargs:
         model.freeze_batchnorm(bool(kwargs["freeze_bn"]))
+    with_grad_diff(criterion, kwargs.get("grad_diff_weight"), kwargs.get("grad_diff_kwargs"))
     with_roi_mean(criterion, kwargs.get("roi_mean_weight"), kwargs.get("roi_mean_kwargs"))
     with_ssim(criterion, kwargs.get("ssim_weight"), kwargs.get("ssim_kwargs"))
     augment = kwargs.get("augment")

@@ -442,6 +442,24 @@ int coma_roi_mean_bwd(const coma_tensor* roi, const int32_t* roi_ids, int32_t n_
 int coma_roi_region_stats(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi,
                           const int32_t* roi_ids, int32_t n_roi, double* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- gradient-difference loss (csrc/grad_diff.hip): an edge term on forward differences.  Per sample, axis a in {z, y, x}
+ * and every voxel v whose neighbour v + e_a is inside the volume:
+ *   gp = pred[v + e_a] - pred[v], gg = gt[v + e_a] - gt[v], t = |gp| - |gg| (mode 0, "abs") | gp - gg (mode 1, "signed")
+ *   phi(t) = |t| (alpha 1) | t^2 (alpha 2);  m_a(v) = 1 (roi NULL) | [roi[v] != 0 and roi[v + e_a] != 0]
+ *   loss = sum_a axis_w[a] S_a / N_a,  S_a = sum_v m_a phi(t),  N_a = sum_v m_a  (an axis with N_a = 0 contributes 0)
+ *   coef[b][a] = axis_w[a] / N_a  (0 if N_a = 0);  sign(0) = 0 in every derivative
+ * axis_w: three HOST floats (z, y, x), finite and >= 0, read at the call.  loss: B floats; coef: B x 3 floats (device).
+ * pred: fp32 or bf16, C = 1, any voxel pitch; gt: pred's dtype, voxel pitch 1; roi: fp32, voxel pitch 1, or NULL.
+ * One pass over 8 x 8 x 32 tiles staged in LDS, fp64 arithmetic on the staged values, one fp64 record per tile in ws, a
+ * fixed-order finalise: no atomics, no host read, bitwise repeatable, the same bits from 16-byte and element-wise staging. */
+size_t coma_grad_diff_ws_bytes(const coma_tensor* pred);
+int coma_grad_diff_fwd(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi, int32_t mode, int32_t alpha,
+                       const float* axis_w, float* loss, float* coef, void* ws, size_t ws_bytes, void* stream);
+/* dpred[v] (=) gout[b] * sum_a coef[b][a] * (psi_a(v - e_a) - psi_a(v)), psi_a(v) = m_a(v) phi'(t) chi, chi = sign(gp) (abs)
+ * | 1 (signed), 0 where the pair does not exist.  dpred: pred's dtype, any voxel pitch; every voxel is assigned once. */
+int coma_grad_diff_bwd(const coma_tensor* pred, const coma_tensor* gt, const coma_tensor* roi, int32_t mode, int32_t alpha,
+                       const float* gout, const float* coef, const coma_tensor* dpred, void* stream);
+
 /* ---- evaluation statistics: one pass over (pred, gt, roi) giving, per sample and per
  *      bin (n_roi ROIs + the whole volume), the sums behind calc_roi_metrics (attn_unet_data_parallel.py:1361-1397),
  *      the global MAE/MAPE/RSE/RRMSE of contrastive_test (:1214-1231) and RoiCorrMetric (:49-60).
